@@ -20,7 +20,14 @@ WORLD_SIZE must equal N; otherwise bench.py exits non-zero rather than report an
 Inputs (scene, BVH, camera) are resident in HBM before the timed region. Scaling is strong: the
 frame is fixed as N grows.
 
-Also reported on the same line:
+A plain run sets up, warms up, times --steps steps and prints the line: `value`, `ms_per_step`
+and the configuration. --dump-outputs DIR also writes what the last timed step computed, as
+DIR/frame_xyz.npy (float64, H x W x 3: the frame's accumulated CIE XYZ) and DIR/rgba8.npy (float32,
+H x W x 4: the finalized sRGB RGBA8 bytes as numbers); the inputs are seeded, so two builds run
+with the same arguments can be compared value for value.
+
+With --full the line also carries (each takes device or host runs of its own, after the timed
+steps):
   roofline      the render kernel's average launch duration (HIP events the library records on
                 the stream it launches on) against the f64 VALU peak, with ALGORITHMIC FLOPs =
                 the kernel's own work counters (an untimed instrumented launch of the same frame)
@@ -84,14 +91,20 @@ def parse():
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=3)
     ap.add_argument("--warmup", type=int, default=1)
-    ap.add_argument("--cpu-spp", type=int, default=128, help="spp of the CPU-baseline sample (0 = skip)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also measure the roofline record (one-stream kernel-time frames, "
+                         "instrumented launch), the david sub-record and the CPU baseline, and for N > 1 check the "
+                         "assembled frame against a one-device render")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the last timed step's outputs to DIR/frame_xyz.npy (float64) and DIR/rgba8.npy (float32)")
+    ap.add_argument("--cpu-spp", type=int, default=128, help="--full: spp of the CPU-baseline sample (0 = skip)")
     ap.add_argument("--cpu-threads", type=int, default=0,
                     help="host threads for the CPU baseline (0 = the CPUs this process may use, at most 16: "
                          "the GPU box's share per GPU)")
-    ap.add_argument("--no-stats", action="store_true", help="skip the instrumented launch (roofline = null)")
+    ap.add_argument("--no-stats", action="store_true", help="--full: skip the instrumented launch (roofline = null)")
     ap.add_argument("--spu", type=int, default=0, help="samples per work unit (0 = library's choice)")
     ap.add_argument("--david-spp", type=int, default=64,
-                    help="spp of the david (configs[4]) sub-record (0 = skip it)")
+                    help="--full: spp of the david (configs[4]) sub-record (0 = skip it)")
     ap.add_argument("--david-frames", type=int, default=2, help="timed frames of the david sub-record")
     ap.add_argument("--streams", type=int, default=2,
                     help="frames alternate over this many HIP streams (2: the next frame's render fills the SIMD "
@@ -355,6 +368,16 @@ def _event(st):
     return ev
 
 
+def dump_outputs(out_dir, frame, rgba):
+    """--dump-outputs: what a caller of the timed path receives from its last step, whole (15.4 MB +
+    10.2 MB at 800x800): the frame's accumulated XYZ as float64, the finalized RGBA8 bytes as float32."""
+    import numpy as np
+    out = Path(out_dir)
+    out.mkdir(parents=True, exist_ok=True)
+    np.save(out / "frame_xyz.npy", frame.cpu().numpy())
+    np.save(out / "rgba8.npy", rgba.cpu().numpy().astype(np.float32))
+
+
 def main():
     a = parse()
     mode, world, rank, local = launch_mode(a)
@@ -541,12 +564,14 @@ def main():
             t = torch.tensor([elapsed], dtype=torch.float64)
             dist.all_reduce(t, op=dist.ReduceOp.MAX)
             elapsed = float(t.item())
+    if rank == 0 and a.dump_outputs:  # before any later frame reuses the buffers
+        dump_outputs(a.dump_outputs, frames[(a.steps - 1) % S], rgbas[(a.steps - 1) % S])
     render_ms, accum_ms, nfr = drain_timing()
     overlap_ms = render_ms / max(1, nfr)  # k_render launch durations in the timed loop (overlapping for S > 1)
     # The roofline's kernel time: k_render alone. With S > 1 the launches in the timed loop overlap
     # (a launch's events bracket its wait for the slots the previous frame still holds), so the
     # kernel's own duration is taken from 3 frames on one stream right after the timed region.
-    if S > 1:
+    if a.full and S > 1:
         gather_evs.clear()
         with wd.stage("kernel-time frames (one stream)", frames_deadline(3), where):
             for i in range(3):
@@ -575,7 +600,7 @@ def main():
     if rank == 0:  # the image really is the frame: finite, non-zero, and for N > 1 bitwise one device's
         f = frame.float()
         assert torch.isfinite(f).all() and f.abs().sum() > 0
-        if world > 1:
+        if a.full and world > 1:
             full = torch.zeros_like(frame)
             with wd.stage("frame check (one-device render of the whole frame)", frames_deadline(1)):
                 scene.render_async(cam, yart.render_params(W, H, spp, depth), full.data_ptr(), stream.cuda_stream)
@@ -587,7 +612,7 @@ def main():
 
     roofline = None
     cpu = None
-    if rank == 0 and not a.no_stats:
+    if a.full and rank == 0 and not a.no_stats:
         # shard 0's counted work (the whole frame at N = 1) over its kernel time
         with wd.stage("work counters (instrumented launch)", frames_deadline(10)):
             _, st = scene.render_with_stats(cam, yart.render_params(W, H, spp, depth, shard_index=0, shard_count=world))
@@ -637,9 +662,9 @@ def main():
         if balance is not None:
             roofline.update(balance)
     david = None
-    if a.david_spp > 0:
+    if a.full and a.david_spp > 0:
         david = david_record(a, mode, world, rank, local, dev, wd, comm, nccl_group, rehearse)
-    if rank == 0 and a.cpu_spp > 0 and world == 1:
+    if a.full and rank == 0 and a.cpu_spp > 0 and world == 1:
         with wd.stage("cpu baseline (oracle on the host cores)", 900.0):
             cpu = cpu_baseline(preset, cam, W, H, a.cpu_spp, depth, a.cpu_threads)
 
@@ -655,7 +680,7 @@ def main():
                        "height": H, "spp": spp, "max_depth": depth, "parallelism": f"pixel-blocks x{world}",
                        "launch": {"single": "one process, one GPU", "multi": "one process, N GPUs",
                                   "ranks": "one process per GPU (torch.distributed.run)"}[mode],
-                       "streams": S, "prep_frames": prep,
+                       "streams": S, "prep_frames": prep, "full": a.full,
                        "collective": collective, "frame_check": frame_check, "seed": yart.DEFAULT_SEED,
                        "build_id": build_id},
             "roofline": roofline, "cpu_baseline": cpu,

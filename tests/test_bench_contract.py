@@ -1,5 +1,5 @@
-"""The bench line's contract, checked on the newest committed GPU run (profiles/r*_bench_cornell.log)
-and the rocprofv3 summary of the same command: the fields the driver and the judge read are
+"""The bench line's contract, checked on the newest committed GPU run of `bench.py --full`
+(profiles/r*_bench_cornell.log; runs older than the option measured everything by default) and the rocprofv3 summary of the same command: the fields the driver and the judge read are
 present, `value` is the frame's samples over the step time, `roofline.frac` is achieved / peak,
 `achieved` is the launch's algorithmic FLOPs over the kernel time, and that kernel time agrees
 with rocprofv3's average k_render duration. CPU only: it reads committed files."""
@@ -145,6 +145,20 @@ def test_device_balance_fields():
     assert b["per_device_gather_ms"] == [0.4, 0.3, 0.5, 0.2]
     assert b["render_max_over_mean"] == pytest.approx(4.30 / 4.15, rel=1e-3)
     assert b["slowest_device"] == 3
+
+
+def test_plain_run_is_the_default_and_full_is_an_option(monkeypatch):
+    """`bench.py --gpus 1 --steps K --warmup W` is the plain run: --full (roofline, david, CPU
+    baseline) and --dump-outputs are off unless given."""
+    sys.path.insert(0, str(ROOT))
+    import importlib
+    bench = importlib.import_module("bench")
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--gpus", "1", "--steps", "7", "--warmup", "2"])
+    a = bench.parse()
+    assert (a.gpus, a.steps, a.warmup, a.full, a.dump_outputs) == (1, 7, 2, False, None)
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--full", "--dump-outputs", "d"])
+    a = bench.parse()
+    assert a.full is True and a.dump_outputs == "d"
 
 
 def test_rehearsal_line_carries_the_per_device_fields():

@@ -258,6 +258,43 @@ def test_bench_gpus_beyond_the_box_exits_nonzero(repo):
         assert r.returncode != 0 and '"n_gpus"' not in r.stdout
 
 
+def test_bench_plain_run_and_dumped_outputs(tmp_path, repo):
+    """A plain `bench.py --gpus 1 --steps K --warmup W` times K steps and prints the headline line
+    with none of the --full records; --dump-outputs writes the last timed step's frame (float64
+    XYZ) and finalized bytes (float32), which are bitwise a direct render of the bench frame and
+    its finalize."""
+    import json  # noqa: PLC0415
+    sys.path.insert(0, str(repo))
+    import bench  # noqa: PLC0415 - the workload's definition, not a run
+    out = tmp_path / "dump"
+    r = subprocess.run([sys.executable, str(repo / "bench.py"), "--gpus", "1", "--steps", "2", "--warmup", "0",
+                        "--dump-outputs", str(out)], capture_output=True, text=True, timeout=300, cwd=str(repo))
+    assert r.returncode == 0, r.stderr[-2000:]
+    lines = [json.loads(l) for l in r.stdout.splitlines() if l.startswith("{")]
+    assert len(lines) == 1
+    b = lines[0]
+    w = bench.WORKLOAD
+    W, H, spp, depth = w["width"], w["height"], w["spp"], w["max_depth"]
+    assert b["steps"] == 2 and b["warmup"] == 0 and b["n_gpus"] == 1 and b["config"]["full"] is False
+    assert b["metric"] == bench.METRIC and b["unit"] == "Msamples/s" and b["dtype"] == "f64"
+    assert b["higher_is_better"] is True and b["ms_per_step"] > 0
+    assert b["value"] == pytest.approx(W * H * spp / (b["ms_per_step"] * 1e-3) / 1e6, rel=2e-3)
+    assert b["roofline"] is None and b["cpu_baseline"] is None and b["david"] is None
+    assert sorted(f.name for f in out.iterdir()) == ["frame_xyz.npy", "rgba8.npy"]
+    frame, rgba = np.load(out / "frame_xyz.npy"), np.load(out / "rgba8.npy")
+    assert frame.dtype == np.float64 and frame.shape == (H, W, 3)
+    assert rgba.dtype == np.float32 and rgba.shape == (H, W, 4)
+    assert frame.nbytes + rgba.nbytes <= 64 << 20
+    p = yart.Preset(w["scene"])
+    d_want = torch.zeros((H, W, 3), dtype=torch.float64, device="cuda:0")
+    yart.DeviceScene(p).render_async(p.camera(W, H), yart.render_params(W, H, spp, depth), d_want.data_ptr(),
+                                     torch.cuda.current_stream().cuda_stream)
+    torch.cuda.synchronize()
+    want = d_want.cpu().numpy()
+    np.testing.assert_array_equal(frame, want)
+    np.testing.assert_array_equal(rgba, O.finalize(want, spp).astype(np.float32))
+
+
 def test_cli_end_to_end(tmp_path, repo):
     """bin/yart --scene cornell-box ... writes the PNG; its pixels are the oracle's finalize of the
     oracle's render, byte for byte."""

@@ -33,18 +33,18 @@ for s in $STEPS; do
     ab) run ${TAG}_ab 1200 bash tools/gpu_mesh_ab.sh ;;
     probe) run ${TAG}_ovf_probe 300 python3 tools/ovf_probe.py ;;
     lanes) run ${TAG}_lane_phases 300 python3 tools/lane_phases.py david 960 540 16 bunny 800 800 16 cornell-box 800 800 16 random-scene 600 400 16 ;;
-    bench_s3) run ${TAG}_bench_cornell_s3 600 python3 bench.py --steps 20 --warmup 5 --streams 3 --cpu-spp 0 --david-spp 0 ;;
+    bench_s3) run ${TAG}_bench_cornell_s3 600 python3 bench.py --full --steps 20 --warmup 5 --streams 3 --cpu-spp 0 --david-spp 0 ;;
     configs_ext) run ${TAG}_bench_configs_ext 600 python3 tools/bench_configs.py --configs E1,E2,E3,E4,E5 ;;
     smoke) run ${TAG}_smoke 300 python3 -c "import __graft_entry__ as g; g.smoke()" ;;
-    bench) run ${TAG}_bench_cornell 600 python3 bench.py --steps 20 --warmup 5 ;;
+    bench) run ${TAG}_bench_cornell 600 python3 bench.py --full --steps 20 --warmup 5 ;;
     prof_cornell) PASSES="trace fetch write valu mix" bash tools/profile.sh || exit 1 ;;
-    prof_cornell_s1) PFX=cornell_s1_ BENCH_ARGS="--steps 3 --warmup 1 --cpu-spp 0 --no-stats --streams 1 --david-spp 0" PASSES="trace" bash tools/profile.sh || exit 1 ;;
+    prof_cornell_s1) PFX=cornell_s1_ BENCH_ARGS="--full --steps 3 --warmup 1 --cpu-spp 0 --no-stats --streams 1 --david-spp 0" PASSES="trace" bash tools/profile.sh || exit 1 ;;
     prof_cornell_more) PFX=cornell_ PASSES="stall mem" bash tools/profile.sh || exit 1 ;;
     prof_david) PFX=david_ PROG="tools/render_once.py david 960 540 16 2" PASSES="trace fetch write valu mix" bash tools/profile.sh || exit 1 ;;
     prof_c4) PFX=c4_ PROG="tools/render_once.py bunny 800 800 32 1" PASSES="trace fetch write" bash tools/profile.sh || exit 1 ;;
     prof_c5) PFX=c5_ PROG="tools/render_once.py david 1920 1080 64 1" PASSES="trace fetch write" bash tools/profile.sh || exit 1 ;;
     rehearse) run ${TAG}_rehearse_n2 300 env YART_BENCH_SAME_DEVICE=1 python3 -m torch.distributed.run --nnodes=1 --nproc-per-node 2 \
-                --master-addr 127.0.0.1 --master-port 29512 bench.py --gpus 2 --steps 3 --warmup 1 --cpu-spp 0 ;;
+                --master-addr 127.0.0.1 --master-port 29512 bench.py --gpus 2 --full --steps 3 --warmup 1 --cpu-spp 0 ;;
     configs)
       PM=""
       [ -f profiles/${TAG}_c4_pmc.json ] && PM="$PM --pmc C4=profiles/${TAG}_c4_pmc.json"
