@@ -4,6 +4,8 @@ The instrumented kernel (yart_render_with_stats, on the frame's own plan: the pe
 chunked frames since r06) counts, from ballots, how many of a wave's 64 lanes
 work each time a phase's code runs: the cooperative mesh walk's node branch and leaf branch (and the
 quads idle in each walk's drain), the camera-ray branch and the scatter branch of the render loop.
+For the persistent list kernel the camera counters count its primary-ray batches (the output says
+which meaning it reports).
 Prints one JSON line per frame:
 
     python tools/lane_phases.py david 960 540 16 [cornell-box 800 800 16 ...]
@@ -30,6 +32,16 @@ def phases(scene, w, h, spp, depth=50):
          "camera_iters_share": frac(st.camera_iters, st.iterations),
          "scatter_iters_share": frac(st.scatter_iters, st.iterations),
          "lanes_with_a_path": frac(st.camera_lanes + st.scatter_lanes, 64 * st.iterations)}
+    # The persistent list kernel starts samples in batches, iterations of their own in which the whole
+    # wave runs the camera branch (kernels.hip k_render, PRIM): no iteration runs both branches, and
+    # the camera counters then count batches and their lanes. The other kernels mix the branches.
+    both = st.camera_iters + st.scatter_iters - st.iterations
+    r["iterations_running_both_branches"] = both
+    r["camera_counters_count"] = ("batches (whole-wave primary-ray iterations) and their lanes" if both == 0 and st.camera_iters
+                                  else "iterations in which some lane started a sample, and those lanes")
+    if both == 0 and st.camera_iters:
+        r["batches"] = st.camera_iters
+        r["iterations_without_batches"] = st.iterations - st.camera_iters
     if st.coop_rounds:
         r.update({
             "walk_rounds": st.coop_rounds,

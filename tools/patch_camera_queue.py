@@ -3,6 +3,9 @@
 # over the block's 64 pixels) not yet formed, the whole wave forms that group's camera rays (lane k:
 # pixel slot k) into LDS; a lane that takes a job reads its ray there instead of running the camera
 # block divergently at the top of the iteration.
+# Since r07 that kernel starts its samples in whole-wave batches (PRIM); the
+# queue belongs to the mixed loop the other kernels keep, so the patch first turns the batches off
+# for it: what it builds is the r04 experiment on this tree, for an A/B against the batches.
 import sys
 p = sys.argv[1]
 s = open(p).read()
@@ -10,16 +13,20 @@ def rep(old, new):
     global s
     assert s.count(old) == 1, old[:100]
     s = s.replace(old, new, 1)
-rep('''  __shared__ uint32_t s_job[JOBL ? 4 * 6 * 64 : JOBL3 ? 4 * 3 * 64 : 1];''',
-'''  __shared__ uint32_t s_job[JOBL ? 4 * 6 * 64 : JOBL3 ? 4 * 3 * 64 : 1];
+rep('''  constexpr bool PRIM = DYN && !HAS_MESH && !BVH && !EXT;''',
+'''  constexpr bool PRIM = false;  // the mixed loop, with the camera-ray queue below''')
+rep('''  __shared__ uint32_t s_job[JOBL ? 4 * kJobWords * 64 : JOBL3 ? 4 * 3 * 64 : 1];''',
+'''  __shared__ uint32_t s_job[JOBL ? 4 * kJobWords * 64 : JOBL3 ? 4 * 3 * 64 : 1];
   constexpr bool CQ = DYN && !HAS_MESH && !BVH && !EXT;
   __shared__ double s_cam[CQ ? 4 * 2 * 7 * 64 : 1];''')
 rep('''  uint32_t* stk = &s_stack[HAS_MESH ? (wave * kWaveLdsWords + lane) : BVH ? (wave * kStackSlots * 64 + lane) : 0];''',
 '''  uint32_t* stk = &s_stack[HAS_MESH ? (wave * kWaveLdsWords + lane) : BVH ? (wave * kStackSlots * 64 + lane) : 0];
   double* const cq = &s_cam[CQ ? wave * 2 * 7 * 64 + lane : 0];
   uint32_t cq_have0 = 0xFFFFFFFFu, cq_have1 = 0xFFFFFFFFu;  // the group each buffer holds (wave-uniform)''')
-rep('''          local_blk = u / A.n_chunks; chunk_id = u % A.n_chunks;''',
-'''          local_blk = u / A.n_chunks; chunk_id = u % A.n_chunks;
+rep('''(profiles/r05m_ab_unit_order.log)
+          local_blk = u / A.n_chunks; chunk_id = u % A.n_chunks;''',
+'''(profiles/r05m_ab_unit_order.log)
+          local_blk = u / A.n_chunks; chunk_id = u % A.n_chunks;
           cq_have0 = 0xFFFFFFFFu; cq_have1 = 0xFFFFFFFFu;''')
 rep('''        const uint32_t rank = __builtin_amdgcn_mbcnt_hi((uint32_t)(m >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)m, 0u));
         const uint32_t avail = n_jobs - next_job;''',
@@ -62,9 +69,9 @@ rep('''          if ((cov >> slot) & 1ull) { fresh = true; need = false; }''',
               depth = A.max_depth;
             }
           }''')
-rep('''      if (fresh) {  // main.rs:692-698
-        uint32_t jx = x, jy = y;''', '''      if (CQ && fresh) {  // the ray came with the job
+rep('''      if (start) {  // main.rs:692-698
+        uint32_t jx = x, jy = y;''', '''      if (CQ && start) {  // the ray came with the job
         fresh = false;
-      } else if (fresh) {  // main.rs:692-698
+      } else if (start) {  // main.rs:692-698
         uint32_t jx = x, jy = y;''')
 open(p, 'w').write(s)

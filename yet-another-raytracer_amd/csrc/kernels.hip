@@ -2237,11 +2237,15 @@ constexpr int kMeshWavesPerEu = 4;
 // next ray and throughput, or its end. One body for both math policies (the Fast cores first; a
 // lane whose operand left a core's range re-runs it on the IEEE sequences from the same inputs
 // and the same draws) and for both render paths (k_render's fused loop, k_wf_shade).
-template <bool EXT, bool STATS, bool SHARE, class MP>
+// OPQ (k_render's PRIM kernels), against the loop invariants this body leaves in VGPRs for the whole
+// render loop (with them that kernel spilled to scratch): the light count is made opaque where
+// gen_index takes it, so its rejection zone is formed on that path (more than two lights), and the
+// caller passes 1 / n_lights in `lweight`, formed once and held in an SGPR pair.
+template <bool EXT, bool STATS, bool SHARE, bool OPQ = false, class MP>
 __device__ __forceinline__ void scatter_at(const DevScene& S, MP& mp, Rng& g, const V3& hp, const V3& hn, uint32_t hmat,
                                            double hu, double hv, int wbin, const Ray& ray, double T, uint32_t depth,
                                            Stats& st, double& T_, V3& o_, V3& d_, uint32_t& depth_, double& R_,
-                                           bool& term_) {
+                                           bool& term_, double lweight = 0.0) {
   // o_ starts at the hit point, not the incoming ray's origin: only an ended path keeps the initial
   // value, and nothing reads its ray again; the origin then dies with the world pass that used it
   // instead of living (spilled) around the loop to here.
@@ -2267,7 +2271,12 @@ __device__ __forceinline__ void scatter_at(const DevScene& S, MP& mp, Rng& g, co
         if (S.n_lights <= 2) {  // k = 0 for every lane (gen_index(g, 1) draws nothing): scalar loads
           dir = light_random(uniform_at(S.lights, 0u), hp, g, mp);
         } else {
-          const uint32_t k = (uint32_t)gen_index(g, S.n_lights - 1);
+          uint32_t nl1 = S.n_lights - 1;
+          if (OPQ) {
+            nl1 = __builtin_amdgcn_readfirstlane(nl1);  // uniform (a scene constant); says so where control diverged
+            asm volatile("" : "+s"(nl1));
+          }
+          const uint32_t k = (uint32_t)gen_index(g, nl1);
           dir = light_random(S.lights[k], hp, g, mp);
         }
       } else {
@@ -2275,7 +2284,7 @@ __device__ __forceinline__ void scatter_at(const DevScene& S, MP& mp, Rng& g, co
       }
       // hittable.rs:103-111 (formed on the host and read from the scene record instead, it cost david
       // 0.8 %: profiles/r06x_ab_devweight.log)
-      const double weight = 1.0 / (double)S.n_lights;
+      const double weight = OPQ ? lweight : 1.0 / (double)S.n_lights;
       double sum = -0.0;
       // SHARE: unit_vector(dir) and its length once for the cosine pdf, the scatter pdf and a rect
       // light's pdf, which evaluated them separately (the compiler did not merge them): cornell
@@ -2386,7 +2395,31 @@ __global__ __launch_bounds__(256, HAS_MESH ? kMeshWavesPerEu : kWavesPerEu) void
   // at the next iteration, with the rays the other lanes bring; S.park (the busy-quad threshold, 0 =
   // off) is set for scenes with one mesh object.
   constexpr bool PARK = HAS_MESH && DYN && !EXT && !DEEP;
-  __shared__ uint32_t s_job[JOBL ? 4 * 6 * 64 : JOBL3 ? 4 * 3 * 64 : 1];
+  // PRIM (the persistent analytic list kernel and its STATS twin): primary rays run in batches of
+  // 64 — one sample of the unit's 8x8 block, lane l its slot l — in iterations of their own. When
+  // lanes ask for work and no path waits, the lanes that hold a path park it in the wave's LDS
+  // buffer and the whole wave starts the batch: camera ray, world pass, and the samples that end
+  // there (miss, emitter, depth 0) are stored. At the next hand-out the lanes whose primary ray
+  // found a scattering hit go on with it in registers and the others take the parked paths back,
+  // each scattering in the iteration in which it took one. The loop then runs its blocks by whole
+  // waves: the camera block over a coherent pixel block at full occupancy and once per 64 samples,
+  // the scatter block without lanes masked off for a camera ray; a sample costs one lane-iteration
+  // fewer in the mixed iterations. A parked path is its hit point, normal, incoming direction,
+  // wavelength, throughput (11 f64) and material, bin | slot, pixel, sample, block, depth (6 u32),
+  // SoA [word][entry]; it carries its job's identity because it may outlive its unit. A batch
+  // starts only with the buffer empty and parks at most 64 paths, so 64 entries are enough.
+  // The lane's job words lose x and y: the camera block derives them from the unit and the lane.
+  constexpr bool PRIM = DYN && !HAS_MESH && !BVH && !EXT;
+  constexpr int kRecF64 = 11, kRecU32 = 6, kJobWords = PRIM ? 4 : 6;
+  __shared__ uint32_t s_job[JOBL ? 4 * kJobWords * 64 : JOBL3 ? 4 * 3 * 64 : 1];
+  __shared__ double s_recd[PRIM ? 4 * kRecF64 * 64 : 1];
+  __shared__ uint32_t s_recu[PRIM ? 4 * kRecU32 * 64 : 1];
+  // The launch bounds ask for kWavesPerEu (kMeshWavesPerEu) waves per SIMD, that many 256-thread
+  // workgroups per CU: their LDS must fit the CU's 160 KiB, or the occupancy drops without a word.
+  static_assert(!PRIM || kWavesPerEu * (sizeof(s_job) + sizeof(s_recd) + sizeof(s_recu)) <= 160u * 1024u,
+                "k_render (PRIM): the parked-path buffers and job words of kWavesPerEu workgroups exceed the CU's LDS");
+  static_assert(!HAS_MESH || kMeshWavesPerEu * (sizeof(s_stack) + sizeof(s_job)) <= 160u * 1024u,
+                "k_render (mesh): the walk state and job words of kMeshWavesPerEu workgroups exceed the CU's LDS");
   // the wave index through readfirstlane: uniform, so the per-wave LDS bases live in SGPRs (as a
   // VGPR the mesh walk's stack base was spilled and reloaded at every pop)
   const uint32_t lane = threadIdx.x & 63u, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
@@ -2405,7 +2438,11 @@ __global__ __launch_bounds__(256, HAS_MESH ? kMeshWavesPerEu : kWavesPerEu) void
   uint32_t x = bx0 + (slot & 7u), y = by0 + (slot >> 3);
   const uint32_t W = A.width, H = A.height;
   const bool active = x < W && y < H && covered(x, W) && covered(y, H);
-  uint32_t* const jl = &s_job[JOBL ? wave * 6 * 64 + lane : JOBL3 ? wave * 3 * 64 + lane : 0];
+  uint32_t* const jl = &s_job[JOBL ? wave * kJobWords * 64 + lane : JOBL3 ? wave * 3 * 64 + lane : 0];
+  double* const recd = &s_recd[PRIM ? wave * kRecF64 * 64 : 0];  // PRIM: this wave's parked paths
+  uint32_t* const recu = &s_recu[PRIM ? wave * kRecU32 * 64 : 0];
+  uint32_t rec_n = 0;  // PRIM: paths parked, entries [0, rec_n) (wave-uniform)
+  bool batch = false;  // PRIM: this iteration is a batch, its running lanes start a sample (wave-uniform)
   constexpr bool JL = JOBL || JOBL3;
   uint32_t* stk = &s_stack[HAS_MESH ? (wave * kWaveLdsWords + lane) : BVH ? (wave * kStackSlots * 64 + lane) : 0];
   uint8_t* coop = reinterpret_cast<uint8_t*>(&s_stack[HAS_MESH ? wave * kWaveLdsWords : 0]);
@@ -2443,10 +2480,91 @@ __global__ __launch_bounds__(256, HAS_MESH ? kMeshWavesPerEu : kWavesPerEu) void
   int wbin = 0;                         // spectrum bin of the path's wavelength
   g.k0 = (uint32_t)A.seed; g.k1 = (uint32_t)(A.seed >> 32);
 
+  double lweight = 0.0;  // PRIM: scatter_at's 1 / n_lights (hittable.rs:103-111), uniform: an SGPR pair
+  if (PRIM) {
+    const double w = 1.0 / (double)S.n_lights;
+    const uint32_t lo = __builtin_amdgcn_readfirstlane(lo_word(w)), hi = __builtin_amdgcn_readfirstlane((uint32_t)hi_word(w));
+    lweight = __longlong_as_double((long long)(((uint64_t)hi << 32) | lo));
+  }
+
   // The loop exits wave-uniformly: a lane without work stays in it with `run` false, so the
   // mesh walk (qbvh_coop) is reached by all 64 lanes together.
   for (;;) {
-    if (DYN) {
+    if constexpr (PRIM) {
+      // paths may still be parked when the queue is drained: the askers take them
+      uint64_t m = (drained && rec_n == 0u) ? 0ull : __ballot(need);
+      batch = false;
+      while (m) {  // wave-uniform: until every asking lane has a path, or the wave starts a batch
+        if (rec_n == 0u) {
+          if (drained) break;
+          if (next_job >= n_jobs) {  // claim the next unit (as below; one counter for the list walk)
+            const uint32_t first = (uint32_t)__builtin_ctzll(__ballot(true));
+            uint32_t v = 0;
+            if (lane == first) {
+              v = atomicAdd(A.queue, 1u);
+              if (A.progress)
+                __hip_atomic_store(A.progress, A.progress_base + (v < A.n_units ? v + 1u : A.n_units), __ATOMIC_RELAXED,
+                                   __HIP_MEMORY_SCOPE_SYSTEM);
+            }
+            const uint32_t u = (uint32_t)__builtin_amdgcn_readlane((int)v, (int)first);
+            if (u >= A.n_units) { drained = true; break; }
+            local_blk = u / A.n_chunks; chunk_id = u % A.n_chunks;
+            b = A.shard_index + local_blk * A.shard_count;
+            bx0 = (b % A.blocks_x) * 8; by0 = (b / A.blocks_x) * 8;
+            s_lo = A.s_begin + chunk_id * A.chunk;
+            const uint32_t stop = s_lo + A.chunk < s_end ? s_lo + A.chunk : s_end;
+            n_jobs = (stop > s_lo ? stop - s_lo : 0) * 64;
+            next_job = 0;
+            const uint32_t cx = bx0 + (lane & 7u), cy = by0 + (lane >> 3);
+            cov = __ballot(cx < W && cy < H && covered(cx, W) && covered(cy, H));
+            if (cov == 0ull) n_jobs = 0;  // a block outside the crop grid has no jobs: a batch has a lane
+            continue;
+          }
+          {  // park the paths
+            const uint64_t pm = __ballot(!need);
+            if (!need) {
+              const uint32_t e = __builtin_amdgcn_mbcnt_hi((uint32_t)(pm >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)pm, 0u));
+              recd[e] = hp.x; recd[64 + e] = hp.y; recd[128 + e] = hp.z;
+              recd[192 + e] = hn.x; recd[256 + e] = hn.y; recd[320 + e] = hn.z;
+              recd[384 + e] = ray.d.x; recd[448 + e] = ray.d.y; recd[512 + e] = ray.d.z;
+              recd[576 + e] = ray.wl; recd[640 + e] = T;
+              recu[e] = hmat; recu[64 + e] = ((uint32_t)wbin << 6) | jl[192];
+              recu[128 + e] = jl[0]; recu[192 + e] = jl[64]; recu[256 + e] = jl[128]; recu[320 + e] = depth;
+            }
+            rec_n = (uint32_t)__popcll(pm);
+          }
+          // the batch: the unit's next sample, every lane its own slot of the block; a slot outside
+          // the frame or the crop grid sits this iteration out
+          jl[0] = (by0 + (lane >> 3)) * W + bx0 + (lane & 7u);
+          jl[64] = s_lo + (next_job >> 6); jl[128] = local_blk; jl[192] = lane;
+          next_job += 64u;
+          batch = true;
+          need = !((cov >> lane) & 1ull);
+          // no lane has a hit now: as at the hit hand-over below, so that the parked values are dead
+          hp = mk(0.0, 0.0, 0.0); hn = hp; hmat = 0u;
+          __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");  // other lanes read the parked paths later
+          break;
+        }
+        const uint32_t rank = __builtin_amdgcn_mbcnt_hi((uint32_t)(m >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)m, 0u));
+        if (need && rank < rec_n) {  // the first askers take the parked paths, from the top
+          const uint32_t e = rec_n - 1u - rank;
+          hp = mk(recd[e], recd[64 + e], recd[128 + e]);
+          hn = mk(recd[192 + e], recd[256 + e], recd[320 + e]);
+          ray.d = mk(recd[384 + e], recd[448 + e], recd[512 + e]);
+          ray.wl = recd[576 + e]; T = recd[640 + e];
+          hmat = recu[e];
+          const uint32_t bs = recu[64 + e];
+          wbin = (int)(bs >> 6);
+          jl[0] = recu[128 + e]; jl[64] = recu[192 + e]; jl[128] = recu[256 + e]; jl[192] = bs & 63u;
+          depth = recu[320 + e];
+          need = false;
+        }
+        const uint32_t given = (uint32_t)__popcll(m);
+        rec_n -= given < rec_n ? given : rec_n;
+        m = __ballot(need);
+      }
+    }
+    if (DYN && !PRIM) {
       uint64_t m = drained ? 0ull : __ballot(need);
       while (m) {  // wave-uniform: hand out jobs until every asking lane has one
         if (next_job >= n_jobs) {  // claim the next unit
@@ -2522,12 +2640,13 @@ __global__ __launch_bounds__(256, HAS_MESH ? kMeshWavesPerEu : kWavesPerEu) void
       }
     }
     const bool run = DYN ? !need : alive;  // DYN: a lane still asking has found the queue drained
+    const bool start = PRIM ? batch : fresh;  // this lane, if it runs, starts a sample
     if (__ballot(run) == 0) break;
     // T is the path's throughput while it runs and its result R (ray_reflectance's return value)
     // once it has ended (term): one register pair for both, since no lane needs both at once.
     bool term = false, want = PARK && parked;  // a parked lane's ray, T and depth are as they were
     if (STATS) {
-      const uint64_t cam = __ballot(run && fresh), sca = __ballot(run && !fresh);
+      const uint64_t cam = __ballot(run && start), sca = __ballot(run && !start);
       if (lane == 0) {
         st.v[ST_ITERS]++;
         st.v[ST_CAMERA_LANES] += (uint32_t)__popcll(cam);
@@ -2540,10 +2659,11 @@ __global__ __launch_bounds__(256, HAS_MESH ? kMeshWavesPerEu : kWavesPerEu) void
       // One Philox site per iteration for every lane: blocks 0-1 of this iteration's phase, the
       // camera ray of a fresh sample (phase 0) or the scatter of the hit the previous iteration
       // found (phase max_depth - depth + 1, its bounce level).
-      rng_phase<!HAS_MESH && !BVH>(g, JL ? jl[0] : pixel, JL ? jl[64] : smp, fresh ? 0u : A.max_depth - depth + 1u);
-      if (fresh) {  // main.rs:692-698
+      rng_phase<!HAS_MESH && !BVH>(g, JL ? jl[0] : pixel, JL ? jl[64] : smp, start ? 0u : A.max_depth - depth + 1u);
+      if (start) {  // main.rs:692-698
         uint32_t jx = x, jy = y;
-        if (JOBL) { jx = jl[256]; jy = jl[320]; }
+        if (JOBL && !PRIM) { jx = jl[256]; jy = jl[320]; }
+        if (PRIM) { jx = bx0 + (lane & 7u); jy = by0 + (lane >> 3); }  // a batch lane: its slot of the wave's unit
         if (JOBL3) { const uint32_t p = jl[0]; jy = p / W; jx = p - jy * W; }
         // W - 1 and H - 1 opaque here: hoisted, their f64 conversions held two VGPR pairs through the
         // whole loop (the mesh kernel spilled them)
@@ -2563,7 +2683,7 @@ __global__ __launch_bounds__(256, HAS_MESH ? kMeshWavesPerEu : kWavesPerEu) void
         // One body, two math policies: the Fast cores first; a lane with an operand outside a
         // core's range re-runs it on the IEEE sequences from the same inputs and the same draws.
         auto scatter = [&](auto& mp, double& T_, V3& o_, V3& d_, uint32_t& depth_, double& R_, bool& term_) {
-          scatter_at<EXT, STATS, !HAS_MESH>(S, mp, g, hp, hn, hmat, hu, hv, wbin, ray, T, depth, st, T_, o_, d_, depth_, R_, term_);
+          scatter_at<EXT, STATS, !HAS_MESH, PRIM>(S, mp, g, hp, hn, hmat, hu, hv, wbin, ray, T, depth, st, T_, o_, d_, depth_, R_, term_, lweight);
         };
         double nT, nR;
         V3 no, nd;
