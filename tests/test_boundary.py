@@ -194,6 +194,30 @@ def test_render_multi_async_evicts_slots_beyond_eight_caller_streams():
     m.close()
 
 
+def test_render_multi_regrows_its_buffers_between_frames():
+    """One multi handle, one device, one caller stream: a 16x16 frame, then 48x40 (the slot's packed
+    shard and the root's receive buffer grow, after the slot's stream drained), then 16x16 again in
+    the buffers it has; then the same three through yart_render_multi, whose own frame buffer grows
+    the same way. Each frame bitwise yart_render with the same parameters."""
+    p = yart.Preset("cornell-box")
+    single = yart.DeviceScene(p)
+    m = yart.MultiScene(p, [0])
+    st = torch.cuda.current_stream()
+    jobs = [(p.camera(W, H), yart.render_params(W, H, 4, 50)) for W, H in [(16, 16), (48, 40), (16, 16)]]
+    refs = [single.render(cam, prm) for cam, prm in jobs]
+    outs = [torch.full(ref.shape, float("nan"), dtype=torch.float64, device="cuda:0") for ref in refs]
+    for (cam, prm), out in zip(jobs, outs):
+        m.render_async(cam, prm, out.data_ptr(), st.cuda_stream)
+    torch.cuda.synchronize()
+    for k, (out, ref) in enumerate(zip(outs, refs)):
+        np.testing.assert_array_equal(out.cpu().numpy(), ref, err_msg=f"async frame {k}")
+    assert m.frame_timing()[2] == 3
+    for k, ((cam, prm), ref) in enumerate(zip(jobs, refs)):
+        np.testing.assert_array_equal(m.render(cam, prm), ref, err_msg=f"host frame {k}")
+    assert (refs[1][O.coverage(48, 40)].sum(axis=-1) != 0).mean() > 0.05  # not frames of zeros
+    m.close()
+
+
 def test_wavefront_frames_back_to_back_on_one_stream():
     """ADVICE r03 (status-ring race): on the wavefront path a pass ends at a data-dependent
     iteration j while iterations j+1 .. j+6 are still queued; the next pass or frame on the same

@@ -773,6 +773,31 @@ def test_scratch_pass_shrinks_when_the_device_is_nearly_full(dev):
     assert (got[O.coverage(W, H)].sum(axis=-1) != 0).mean() > 0.5
 
 
+def test_sample_scratch_regrows_between_frames_on_one_stream(dev):
+    """Chunked frames (samples_per_unit = 2) enqueued back to back on one stream: 16x16x4, then
+    48x40x8 (the stream's sample scratch grows, after the stream drained), then 16x16x4 again in the
+    larger scratch. Each frame bitwise its render on a fresh scene handle; the three frames' timing
+    events were handed over to the scene and are read (and recycled) by yart_frame_timing."""
+    import torch
+    p = yart.Preset("cornell-box")
+    s = yart.DeviceScene(p)
+    st = torch.cuda.current_stream()
+    shapes = [(16, 16, 4), (48, 40, 8), (16, 16, 4)]
+    outs = []
+    for W, H, spp in shapes:
+        out = torch.full((H, W, 3), float("nan"), dtype=torch.float64, device="cuda:0")
+        s.render_async(p.camera(W, H), yart.render_params(W, H, spp, 50, samples_per_unit=2), out.data_ptr(), st.cuda_stream)
+        outs.append(out)
+    torch.cuda.synchronize()
+    for (W, H, spp), out in zip(shapes, outs):
+        ref = yart.DeviceScene(p).render(p.camera(W, H), yart.render_params(W, H, spp, 50, samples_per_unit=2))
+        np.testing.assert_array_equal(out.cpu().numpy(), ref, err_msg=f"{W}x{H}x{spp}")
+    assert (outs[1].cpu().numpy()[O.coverage(48, 40)].sum(axis=-1) != 0).mean() > 0.05  # not a frame of zeros
+    r, a, n = s.frame_timing(st.cuda_stream)
+    assert n == 3 and r > 0 and a > 0
+    assert s.frame_timing(st.cuda_stream)[2] == 0  # read once
+
+
 def test_auto_chunking_at_full_device_scale(dev):
     """A small frame on a 256-CU device is auto-split into sample chunks; still bitwise."""
     p = yart.Preset("cornell-box")

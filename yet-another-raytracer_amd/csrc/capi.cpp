@@ -84,15 +84,14 @@ double spectrum_bin(const double rgb[3], int i) {
 }
 
 template <class T>
-hipError_t upload(std::vector<void*>& owned, const T* src, size_t n, const T** dst, uint64_t& bytes) {
+hipError_t upload(std::vector<DevBuf>& owned, const T* src, size_t n, const T** dst, uint64_t& bytes) {
   if (n == 0) { *dst = nullptr; return hipSuccess; }
-  void* p = nullptr;
-  hipError_t e = hipMalloc(&p, sizeof(T) * n);
-  if (e != hipSuccess) return e;
-  owned.push_back(p);
+  DevBuf b;
+  if (hipError_t e = b.alloc(sizeof(T) * n)) return e;
   bytes += sizeof(T) * n;
-  *dst = static_cast<const T*>(p);
-  return hipMemcpy(p, src, sizeof(T) * n, hipMemcpyHostToDevice);
+  *dst = b.get<const T>();
+  owned.push_back(std::move(b));
+  return hipMemcpy(owned.back().get<void>(), src, sizeof(T) * n, hipMemcpyHostToDevice);
 }
 
 bool valid_objects(const yart_scene_desc* d, const yart_object* o, uint32_t n, bool lights, std::string& why) {
@@ -141,24 +140,14 @@ DevObject to_dev(const yart_object& o) {
 }  // namespace
 
 yart_scene::~yart_scene() {
+  // everything that owns a HIP resource goes here, while the scene's device is current (the guard
+  // is gone by the time the members are destroyed); the device buffers' release waits for the device
   DeviceGuard g(device);
-  for (void* p : owned) (void)hipFree(p);
-  for (auto& kv : streams) {
-    (void)hipFree(kv.second->scratch);
-    if (kv.second->wf_mem) (void)hipFree(kv.second->wf_mem);
-    if (kv.second->ovf) (void)hipFree(kv.second->ovf);
-    if (kv.second->wf_status_host) (void)hipHostFree(kv.second->wf_status_host);
-    StreamState& t = *kv.second;
-    for (hipStream_t x : {t.aux, t.acc})
-      if (x) (void)hipStreamDestroy(x);
-    for (hipEvent_t e : {t.ev_start, t.ev_render[0], t.ev_render[1], t.ev_acc[0], t.ev_acc[1]})
-      if (e) (void)hipEventDestroy(e);
-  }
-  for (hipStream_t st : owned_streams) (void)hipStreamDestroy(st);
-  for (auto& kv : frames)
-    for (auto& f : kv.second)
-      for (hipEvent_t e : f) (void)hipEventDestroy(e);
-  for (hipEvent_t e : event_pool) (void)hipEventDestroy(e);
+  owned.clear();
+  streams.clear();
+  owned_streams.clear();
+  frames.clear();  // the unread frames' leases, back into the pool
+  event_pool.clear();
 }
 
 extern "C" {
@@ -616,20 +605,19 @@ StreamState* stream_state(yart_scene* s, hipStream_t stream) {
   return e.get();
 }
 
+// The streams earlier frames of `stream` may still run on (their overlapped passes too): what a
+// buffer of the stream's state waits for before it is replaced.
+struct FrameStreams {
+  hipStream_t s[3];
+  size_t n;
+  FrameStreams(const StreamState* st, hipStream_t stream) : s{stream, st->aux, st->acc}, n(st->acc ? 3 : 1) {}
+};
+
 // The walk stacks' HBM overflow of a stream (deep meshes), grown on demand like the scratch.
 int stream_ovf(StreamState* st, hipStream_t stream, size_t bytes, uint32_t** out) {
-  if (st->ovf_bytes < bytes) {
-    if (st->ovf) {
-      HIP_TRY(hipStreamSynchronize(stream), "drain the stream before growing its stack overflow");
-      for (hipStream_t x : {st->aux, st->acc})
-        if (x) HIP_TRY(hipStreamSynchronize(x), "drain the stream before growing its stack overflow");
-      HIP_TRY(hipFree(st->ovf), "hipFree stack overflow");
-    }
-    st->ovf = nullptr; st->ovf_bytes = 0;
-    HIP_TRY(hipMalloc(&st->ovf, bytes), "hipMalloc stack overflow");
-    st->ovf_bytes = bytes;
-  }
-  *out = st->ovf;
+  const FrameStreams fs(st, stream);
+  HIP_TRY(st->ovf.reserve(bytes, fs.s, fs.n), "grow the stream's stack overflow");
+  *out = st->ovf.get<uint32_t>();
   return YART_OK;
 }
 
@@ -648,20 +636,18 @@ int pass_scratch(StreamState* st, hipStream_t stream, const RenderArgs& a, Plan&
                  double** out, uint32_t halves = 1) {
   for (;;) {
     const size_t bytes = halves * ((size_t)a.n_blocks * pl.pass_spp * 64 * 3 * sizeof(double) + 256);
-    if (st->bytes >= bytes) { *out = st->scratch; return YART_OK; }
-    double* grown = nullptr;
-    const hipError_t e = hipMalloc(&grown, bytes);
+    if (st->scratch.bytes() >= bytes) { *out = st->scratch.get<double>(); return YART_OK; }
+    DevBuf grown;
+    const hipError_t e = grown.alloc(bytes);
     if (e == hipSuccess) {
       if (st->scratch) {
         // earlier frames may still use the old one (their overlapped passes too)
-        hipError_t d = hipStreamSynchronize(stream);
-        for (hipStream_t x : {st->aux, st->acc})
-          if (x && d == hipSuccess) d = hipStreamSynchronize(x);
-        if (d != hipSuccess) { (void)hipFree(grown); return hip_fail(d, "drain the stream before growing its scratch"); }
-        HIP_TRY(hipFree(st->scratch), "hipFree scratch");
+        const FrameStreams fs(st, stream);
+        HIP_TRY(drain(fs.s, fs.n), "drain the stream before growing its scratch");
+        HIP_TRY(st->scratch.release(), "release the old scratch");
       }
-      st->scratch = grown; st->bytes = bytes;
-      *out = st->scratch;
+      st->scratch = std::move(grown);
+      *out = st->scratch.get<double>();
       return YART_OK;
     }
     if (e != hipErrorOutOfMemory || pl.pass_spp <= min_spp) return hip_fail(e, "hipMalloc scratch");
@@ -671,34 +657,12 @@ int pass_scratch(StreamState* st, hipStream_t stream, const RenderArgs& a, Plan&
   }
 }
 
-// n timing events for one frame (copied out: the caller owns them until push_frame hands them over).
-int take_events(yart_scene* s, size_t n, std::vector<hipEvent_t>& f) {
-  f.clear();
-  std::lock_guard<std::mutex> lk(s->mu);
-  while (f.size() < n) {
-    if (!s->event_pool.empty()) {
-      f.push_back(s->event_pool.back());
-      s->event_pool.pop_back();
-    } else {
-      hipEvent_t e;
-      hipError_t err = hipEventCreate(&e);
-      if (err != hipSuccess) {
-        for (hipEvent_t x : f) s->event_pool.push_back(x);
-        f.clear();
-        return hip_fail(err, "hipEventCreate");
-      }
-      f.push_back(e);
-    }
-  }
-  return YART_OK;
-}
-void push_frame(yart_scene* s, hipStream_t stream, std::vector<hipEvent_t>&& f) {
+// A frame's timing events are leased from the scene's pool (a frame that fails half way gives them
+// back) and handed over here once the frame is enqueued, for yart_frame_timing to read and recycle.
+void push_frame(yart_scene* s, hipStream_t stream, EventPool::Lease&& f) {
   std::lock_guard<std::mutex> lk(s->mu);
   auto& frames = s->frames[stream];
-  if (frames.size() >= 4096) {  // never read: recycle the oldest frame's events
-    for (hipEvent_t e : frames.front()) s->event_pool.push_back(e);
-    frames.erase(frames.begin());
-  }
+  if (frames.size() >= 4096) frames.erase(frames.begin());  // never read: recycle the oldest frame's events
   frames.push_back(std::move(f));
 }
 
@@ -709,26 +673,16 @@ constexpr uint32_t kWfStatusRing = 64, kWfSentinel = 0xFFFFFFFFu;
 size_t wf_slot_bytes(uint32_t pool) { return (size_t)pool * (6 * 8 + 2 * 8 + 3 * 8 + 4 * 4) + (size_t)pool / 256 * 8; }
 int stream_wf(StreamState* st, hipStream_t stream, uint32_t pool, WfSlots& q, uint32_t** counters) {
   const size_t bytes = wf_slot_bytes(pool) + 256;
-  if (st->wf_bytes < bytes || st->wf_pool != pool) {
-    if (st->wf_mem) {
-      HIP_TRY(hipStreamSynchronize(stream), "drain the stream before growing its path slots");
-      HIP_TRY(hipFree(st->wf_mem), "hipFree path slots");
-    }
-    st->wf_mem = nullptr; st->wf_bytes = 0; st->wf_pool = 0;
-    HIP_TRY(hipMalloc(&st->wf_mem, bytes), "hipMalloc path slots");
-    st->wf_bytes = bytes; st->wf_pool = pool;
+  // The block is sized by the pool (bytes grows with it), and a frame with another pool size gets a
+  // block of its own size, a smaller one too: not DevBuf::reserve, which would keep the larger block.
+  if (st->wf_pool != pool) {
+    if (st->wf_mem) HIP_TRY(hipStreamSynchronize(stream), "drain the stream before growing its path slots");
+    st->wf_pool = 0;
+    HIP_TRY(st->wf_mem.alloc(bytes), "hipMalloc path slots");
+    st->wf_pool = pool;
   }
-  if (!st->wf_status_host) {
-    void* h = nullptr;
-    HIP_TRY(hipHostMalloc(&h, kWfStatusRing * sizeof(uint32_t), hipHostMallocMapped | hipHostMallocCoherent),
-            "hipHostMalloc status ring");
-    void* d = nullptr;
-    hipError_t e = hipHostGetDevicePointer(&d, h, 0);
-    if (e != hipSuccess) { (void)hipHostFree(h); return hip_fail(e, "hipHostGetDevicePointer"); }
-    st->wf_status_host = static_cast<uint32_t*>(h);
-    st->wf_status_dev = static_cast<uint32_t*>(d);
-  }
-  char* p = static_cast<char*>(st->wf_mem);
+  if (!st->wf_status.host()) HIP_TRY(st->wf_status.alloc(kWfStatusRing * sizeof(uint32_t)), "hipHostMalloc status ring");
+  char* p = st->wf_mem.get<char>();
   auto take = [&](size_t n) { char* r = p; p += n; return r; };
   q.o = reinterpret_cast<double*>(take(3 * 8 * (size_t)pool));
   q.d = reinterpret_cast<double*>(take(3 * 8 * (size_t)pool));
@@ -764,7 +718,7 @@ int wf_pass(yart_scene* s, StreamState* st, const RenderArgs& b, hipStream_t str
   HIP_TRY(hipMemsetAsync(q.job, 0xFF, 4 * (size_t)pool, stream), "empty the path slots");
   HIP_TRY(hipMemsetAsync(q.range, 0, (size_t)pool / 256 * 8, stream), "empty the job ranges");
   HIP_TRY(hipMemsetAsync(cnt, 0, 8 * sizeof(uint32_t), stream), "zero the pass counters");
-  volatile uint32_t* hs = st->wf_status_host;
+  volatile uint32_t* hs = st->wf_status.host();
   WfArgs w;
   w.q = q;
   w.jobs = cnt + 4;
@@ -784,7 +738,7 @@ int wf_pass(yart_scene* s, StreamState* st, const RenderArgs& b, hipStream_t str
     __atomic_store_n(&hs[slot], kWfSentinel, __ATOMIC_RELAXED);
     w.alive = cnt + k % 4;
     w.alive_next = cnt + (k + 1) % 4;
-    w.status = st->wf_status_dev + slot;
+    w.status = st->wf_status.device() + slot;
     HIP_TRY(launch_wf_shade(s->dev, b, w, stream), "launch k_wf_shade");
     HIP_TRY(launch_wf_trace(s->dev, b, w, stream), "launch k_wf_trace");
     st->wf_iter = base + k + 1;
@@ -816,32 +770,13 @@ int launch_frame(yart_scene* s, RenderArgs a, uint32_t requested, bool stats, hi
   Plan pl = plan(s, a, requested);
   StreamState* st = stream_state(s, stream);
   std::lock_guard<std::mutex> frame_lock(st->frame_mu);
-  std::vector<hipEvent_t> ev;
-  if (prog) { a.progress = prog->device; a.progress_count = prog->counter; }
-  if (s->wavefront && !stats) {  // mesh scenes: the wavefront path, pass by pass over the scratch budget
-    double* scratch = nullptr;
-    if (int rc = pass_scratch(st, stream, a, pl, 1, &scratch)) return rc;
-    const uint32_t passes = (a.spp + pl.pass_spp - 1) / pl.pass_spp;
-    if (int rc = take_events(s, 3 * (size_t)passes, ev)) return rc;
-    uint32_t k = 0;
-    for (uint32_t s0 = 0; s0 < a.spp; s0 += pl.pass_spp, ++k) {
-      RenderArgs b = a;
-      b.s_begin = s0;
-      b.s_count = a.spp - s0 < pl.pass_spp ? a.spp - s0 : pl.pass_spp;
-      b.chunk = b.s_count;
-      b.n_chunks = 1;
-      b.scratch = scratch;
-      b.n_units = b.n_blocks;
-      HIP_TRY(hipEventRecord(ev[3 * k], stream), "hipEventRecord");
-      if (int rc = wf_pass(s, st, b, stream)) return rc;
-      HIP_TRY(hipEventRecord(ev[3 * k + 1], stream), "hipEventRecord");
-      HIP_TRY(launch_accumulate(b, s0 == 0, stream), "launch k_accumulate");
-      HIP_TRY(hipEventRecord(ev[3 * k + 2], stream), "hipEventRecord");
-    }
-    if (prog) prog->total_units = 0;
-    push_frame(s, stream, std::move(ev));
-    return YART_OK;
-  }
+  EventPool::Lease ev;  // the frame's timing events: back into the pool unless push_frame gets them
+  if (prog) { a.progress = prog->word.device(); a.progress_count = prog->counter.get<uint32_t>(); }
+  // Mesh scenes on the wavefront path render pass by pass over the scratch budget like a chunked
+  // frame whose passes run one after another on the caller's stream: a pass is one chunk, one unit
+  // per block (down to one sample when the device is nearly full), rendered by wf_pass; it has no
+  // unit counters, no walk-stack overflow and reports no progress units.
+  const bool wf = s->wavefront && !stats;
   // A frame larger than the scratch budget renders in passes, and the passes overlap (r06): the
   // budget is split in two halves, the odd passes render on the stream's `aux` stream into the second
   // half while the previous pass's last waves finish, and k_accumulate adds the passes in pass order
@@ -849,19 +784,19 @@ int launch_frame(yart_scene* s, RenderArgs a, uint32_t requested, bool stats, hi
   // are the same (the accumulates run in order); the frame starts and ends in the caller's stream
   // order. (One pass after another, each pass's tail idled the device: C5 on 16 GiB, 4 passes,
   // -3 %; 8 GiB, 7 passes, -5.6 %; profiles/r06r_ab_scratch_budget.log.)
-  bool overlap = pl.overlap;
+  bool overlap = pl.overlap && !wf;
   uint64_t ovf_words = 0;  // one launch's overflow region (a second one for the overlapped passes)
-  if (s->dev.deep || s->dev.park) {  // the walk stacks' HBM overflow (deep meshes; PARK: the re-walk's
-                                     // stacks): one region per wave of the largest launch below
+  if (!wf && (s->dev.deep || s->dev.park)) {  // the walk stacks' HBM overflow (deep meshes; PARK: the re-walk's
+                                              // stacks): one region per wave of the largest launch below
     const uint64_t fused_waves = (uint64_t)a.n_blocks, dyn_waves = (uint64_t)s->cu_count * 16;
     const uint64_t units = (uint64_t)a.n_blocks * ((pl.pass_spp + pl.chunk - 1) / pl.chunk);
     const uint64_t waves = (pl.chunk >= a.spp ? fused_waves : std::min(dyn_waves, units)) + 4;
     ovf_words = waves * kOvfWords;
     if (int rc = stream_ovf(st, stream, (overlap ? 2 : 1) * ovf_words * sizeof(uint32_t), &a.stack_ovf)) return rc;
   }
-  if (pl.chunk >= a.spp) {  // fused: one unit per block, sums in registers
+  if (!wf && pl.chunk >= a.spp) {  // fused: one unit per block, sums in registers
     if (prog) prog->total_units = a.n_blocks;
-    if (int rc = take_events(s, 2, ev)) return rc;
+    HIP_TRY(s->event_pool.take(2, ev), "hipEventCreate");
     HIP_TRY(hipEventRecord(ev[0], stream), "hipEventRecord");
     HIP_TRY(launch_render(s->dev, a, stats, stream), "launch k_render");
     HIP_TRY(hipEventRecord(ev[1], stream), "hipEventRecord");
@@ -869,27 +804,24 @@ int launch_frame(yart_scene* s, RenderArgs a, uint32_t requested, bool stats, hi
     return YART_OK;
   }
   double* scratch = nullptr;
-  if (int rc = pass_scratch(st, stream, a, pl, pl.chunk, &scratch, overlap ? 2u : 1u)) return rc;
+  if (int rc = pass_scratch(st, stream, a, pl, wf ? 1 : pl.chunk, &scratch, overlap ? 2u : 1u)) return rc;
   overlap = overlap && pl.pass_spp < a.spp;
   if (overlap && !st->acc) {  // the stream's first overlapped frame: its two helper streams and events
     DeviceGuard g(s->device);
-    hipStream_t x[2] = {nullptr, nullptr};
-    hipEvent_t e[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};
-    hipError_t err = hipSuccess;
-    for (int i = 0; i < 2 && err == hipSuccess; ++i) err = hipStreamCreateWithFlags(&x[i], hipStreamNonBlocking);
-    for (int i = 0; i < 5 && err == hipSuccess; ++i) err = hipEventCreateWithFlags(&e[i], hipEventDisableTiming);
-    if (err != hipSuccess) {
-      for (hipStream_t y : x) if (y) (void)hipStreamDestroy(y);
-      for (hipEvent_t y : e) if (y) (void)hipEventDestroy(y);
-      return hip_fail(err, "create the overlapped passes' streams");
-    }
-    st->aux = x[0]; st->acc = x[1];
-    st->ev_start = e[0]; st->ev_render[0] = e[1]; st->ev_render[1] = e[2]; st->ev_acc[0] = e[3]; st->ev_acc[1] = e[4];
+    Stream aux, acc;
+    Event e[5];
+    hipError_t err = aux.create();
+    if (err == hipSuccess) err = acc.create();
+    for (int i = 0; i < 5 && err == hipSuccess; ++i) err = e[i].create();
+    if (err != hipSuccess) return hip_fail(err, "create the overlapped passes' streams");
+    st->aux = std::move(aux); st->acc = std::move(acc);
+    st->ev_start = std::move(e[0]);
+    for (int i = 0; i < 2; ++i) { st->ev_render[i] = std::move(e[1 + i]); st->ev_acc[i] = std::move(e[3 + i]); }
   }
   const size_t half_doubles = (size_t)a.n_blocks * pl.pass_spp * 64 * 3;
   const size_t half_bytes = half_doubles * sizeof(double) + 256;
   const uint32_t passes = (a.spp + pl.pass_spp - 1) / pl.pass_spp;
-  if (int rc = take_events(s, 3 * (size_t)passes, ev)) return rc;
+  HIP_TRY(s->event_pool.take(3 * (size_t)passes, ev), "hipEventCreate");
   if (overlap) {  // the helper streams start after the caller's earlier work
     HIP_TRY(hipEventRecord(st->ev_start, stream), "hipEventRecord");
     HIP_TRY(hipStreamWaitEvent(st->aux, st->ev_start, 0), "hipStreamWaitEvent");
@@ -901,24 +833,29 @@ int launch_frame(yart_scene* s, RenderArgs a, uint32_t requested, bool stats, hi
     const hipStream_t rs = h ? st->aux : stream;      // where it renders
     const hipStream_t as = overlap ? st->acc : stream;  // where it is added
     double* buf = reinterpret_cast<double*>(reinterpret_cast<char*>(scratch) + h * half_bytes);
-    uint32_t* queue = reinterpret_cast<uint32_t*>(buf + half_doubles);
     RenderArgs b = a;
     b.s_begin = s0;
     b.s_count = a.spp - s0 < pl.pass_spp ? a.spp - s0 : pl.pass_spp;
-    b.chunk = pl.chunk;
-    b.n_chunks = (b.s_count + pl.chunk - 1) / pl.chunk;
+    b.chunk = wf ? b.s_count : pl.chunk;
+    b.n_chunks = (b.s_count + b.chunk - 1) / b.chunk;
     b.scratch = buf;
-    b.queue = queue;
     b.n_units = b.n_blocks * b.n_chunks;
-    b.waves = (uint32_t)s->cu_count * 16;  // 4 waves per SIMD resident
-    if (a.stack_ovf) b.stack_ovf = a.stack_ovf + h * ovf_words;
-    b.progress_base = base;
-    base += b.n_units;
-    if (overlap && k >= 2) HIP_TRY(hipStreamWaitEvent(rs, st->ev_acc[h], 0), "hipStreamWaitEvent");
-    // the unit counter, and the 8 XCD-local ones of mesh frames (kernels.hip, claim of a unit)
-    HIP_TRY(hipMemsetAsync(queue, 0, 9 * sizeof(uint32_t), rs), "zero the unit counters");
+    if (!wf) {
+      b.queue = reinterpret_cast<uint32_t*>(buf + half_doubles);
+      b.waves = (uint32_t)s->cu_count * 16;  // 4 waves per SIMD resident
+      if (a.stack_ovf) b.stack_ovf = a.stack_ovf + h * ovf_words;
+      b.progress_base = base;
+      base += b.n_units;
+      if (overlap && k >= 2) HIP_TRY(hipStreamWaitEvent(rs, st->ev_acc[h], 0), "hipStreamWaitEvent");
+      // the unit counter, and the 8 XCD-local ones of mesh frames (kernels.hip, claim of a unit)
+      HIP_TRY(hipMemsetAsync(b.queue, 0, 9 * sizeof(uint32_t), rs), "zero the unit counters");
+    }
     HIP_TRY(hipEventRecord(ev[3 * k], rs), "hipEventRecord");
-    HIP_TRY(launch_render(s->dev, b, stats, rs), "launch k_render");
+    if (wf) {
+      if (int rc = wf_pass(s, st, b, rs)) return rc;
+    } else {
+      HIP_TRY(launch_render(s->dev, b, stats, rs), "launch k_render");
+    }
     HIP_TRY(hipEventRecord(ev[3 * k + 1], rs), "hipEventRecord");
     if (overlap) {
       HIP_TRY(hipEventRecord(st->ev_render[h], rs), "hipEventRecord");
@@ -934,53 +871,37 @@ int launch_frame(yart_scene* s, RenderArgs a, uint32_t requested, bool stats, hi
   return YART_OK;
 }
 
-int acquire_stream(yart_scene* s, hipStream_t* out) {
+int StreamLease::acquire() {
   {
-    std::lock_guard<std::mutex> lk(s->mu);
-    if (!s->idle_streams.empty()) {
-      *out = s->idle_streams.back();
-      s->idle_streams.pop_back();
+    std::lock_guard<std::mutex> lk(s_->mu);
+    if (!s_->idle_streams.empty()) {
+      st_ = s_->idle_streams.back();
+      s_->idle_streams.pop_back();
       return YART_OK;
     }
   }
-  DeviceGuard g(s->device);
-  hipStream_t st;
-  HIP_TRY(hipStreamCreateWithFlags(&st, hipStreamNonBlocking), "hipStreamCreate");
-  std::lock_guard<std::mutex> lk(s->mu);
-  s->owned_streams.push_back(st);
-  *out = st;
+  DeviceGuard g(s_->device);
+  Stream st;
+  HIP_TRY(st.create(), "hipStreamCreate");
+  std::lock_guard<std::mutex> lk(s_->mu);
+  st_ = st;
+  s_->owned_streams.push_back(std::move(st));
   return YART_OK;
 }
-void release_stream(yart_scene* s, hipStream_t st) {
-  std::lock_guard<std::mutex> lk(s->mu);
-  s->idle_streams.push_back(st);
+StreamLease::~StreamLease() {
+  if (!st_) return;
+  (void)hipStreamSynchronize(st_);
+  std::lock_guard<std::mutex> lk(s_->mu);
+  s_->idle_streams.push_back(st_);
 }
 
 int alloc_progress(Progress& p) {
-  void* h = nullptr;
-  HIP_TRY(hipHostMalloc(&h, 64, hipHostMallocMapped | hipHostMallocCoherent), "hipHostMalloc progress word");
-  p.host = static_cast<uint32_t*>(h);
-  __atomic_store_n(p.host, 0u, __ATOMIC_RELAXED);
-  void* d = nullptr;
-  hipError_t e = hipHostGetDevicePointer(&d, h, 0);
-  if (e != hipSuccess) { (void)hipHostFree(h); p.host = nullptr; return hip_fail(e, "hipHostGetDevicePointer"); }
-  p.device = static_cast<uint32_t*>(d);
-  void* c = nullptr;
-  e = hipMalloc(&c, 4);
-  if (e == hipSuccess) e = hipMemset(c, 0, 4);
-  if (e != hipSuccess) {
-    if (c) (void)hipFree(c);
-    (void)hipHostFree(h);
-    p.host = p.device = nullptr;
-    return hip_fail(e, "hipMalloc progress counter");
-  }
-  p.counter = static_cast<uint32_t*>(c);
+  HIP_TRY(p.word.alloc(64), "hipHostMalloc progress word");
+  __atomic_store_n(p.word.host(), 0u, __ATOMIC_RELAXED);
+  hipError_t e = p.counter.alloc(4);
+  if (e == hipSuccess) e = hipMemset(p.counter.get<void>(), 0, 4);
+  if (e != hipSuccess) { p = Progress{}; return hip_fail(e, "hipMalloc progress counter"); }
   return YART_OK;
-}
-void free_progress(Progress& p) {
-  if (p.host) (void)hipHostFree(p.host);
-  if (p.counter) (void)hipFree(p.counter);
-  p.host = p.device = p.counter = nullptr;
 }
 
 int wait_with_progress(const std::vector<hipEvent_t>& done, const std::vector<int>& devices,
@@ -996,7 +917,7 @@ int wait_with_progress(const std::vector<hipEvent_t>& done, const std::vector<in
         // pixels of the frame whose units have been handed out, over all devices
         uint64_t units = 0, total = 0, px = 0;
         for (Progress* p : prog) {
-          const uint32_t u = __atomic_load_n(p->host, __ATOMIC_RELAXED);
+          const uint32_t u = __atomic_load_n(p->word.host(), __ATOMIC_RELAXED);
           units = u < p->total_units ? u : p->total_units;
           total = p->total_units ? p->total_units : 1;
           px += p->pixels * units / total;
@@ -1020,7 +941,7 @@ extern "C" {
 int yart_frame_timing(yart_scene* s, void* stream, double* render_ms, double* accumulate_ms, uint32_t* frames) {
   if (!s || !render_ms || !accumulate_ms || !frames) return fail(YART_ERR_INVALID, "null argument");
   DeviceGuard g(s->device);
-  std::vector<std::vector<hipEvent_t>> mine;
+  std::vector<EventPool::Lease> mine;  // read, then recycled into the pool as it goes
   {
     std::lock_guard<std::mutex> lk(s->mu);
     auto it = s->frames.find((hipStream_t)stream);
@@ -1044,11 +965,6 @@ int yart_frame_timing(yart_scene* s, void* stream, double* render_ms, double* ac
     }
     if (e != hipSuccess && rc == YART_OK) rc = hip_fail(e, "hipEventElapsedTime");
     ++n_frames;
-  }
-  {
-    std::lock_guard<std::mutex> lk(s->mu);
-    for (auto& v : mine)
-      for (hipEvent_t e : v) s->event_pool.push_back(e);
   }
   if (rc != YART_OK) return rc;
   *render_ms = r;
@@ -1096,23 +1012,18 @@ int render_host(yart_scene* s, const yart_camera* cam, const yart_render_params*
   if (int rc = make_args(s, cam, p, nullptr, a)) return rc;
   if (!host_out) return fail(YART_ERR_INVALID, "null output");
   DeviceGuard g(s->device);
-  hipStream_t stream;
-  if (int rc = acquire_stream(s, &stream)) return rc;
-  struct Release {
-    yart_scene* s; hipStream_t st;
-    ~Release() { (void)hipStreamSynchronize(st); release_stream(s, st); }
-  } release{s, stream};
+  StreamLease stream(s);
+  if (int rc = stream.acquire()) return rc;
   const size_t bytes = sizeof(double) * 3 * (size_t)p->width * p->height;
-  double* d_out = nullptr;
-  unsigned long long* d_stats = nullptr;
-  HIP_TRY(hipMalloc(&d_out, bytes), "hipMalloc output");
-  std::unique_ptr<double, decltype(&hipFree)> hold(d_out, &hipFree);
+  DevBuf out, stat_words;
+  HIP_TRY(out.alloc(bytes), "hipMalloc output");
+  double* d_out = out.get<double>();
   HIP_TRY(hipMemsetAsync(d_out, 0, bytes, stream), "hipMemset");
   if (stats) {
-    HIP_TRY(hipMalloc(&d_stats, 25 * sizeof(unsigned long long)), "hipMalloc stats");
-    HIP_TRY(hipMemsetAsync(d_stats, 0, 25 * sizeof(unsigned long long), stream), "hipMemset");
+    HIP_TRY(stat_words.alloc(25 * sizeof(unsigned long long)), "hipMalloc stats");
+    HIP_TRY(hipMemsetAsync(stat_words.get<void>(), 0, 25 * sizeof(unsigned long long), stream), "hipMemset");
   }
-  std::unique_ptr<unsigned long long, decltype(&hipFree)> hold2(d_stats, &hipFree);
+  unsigned long long* d_stats = stat_words.get<unsigned long long>();
   a.out = d_out;
   a.stats = d_stats;
   Progress pr;
@@ -1120,11 +1031,9 @@ int render_host(yart_scene* s, const yart_camera* cam, const yart_render_params*
     if (int rc = alloc_progress(pr)) return rc;
     pr.pixels = shard_pixels(p->width, p->height, a.shard_index, a.shard_count);
   }
-  struct FreeProgress { Progress& p; ~FreeProgress() { free_progress(p); } } free_pr{pr};
   if (int rc = launch_frame(s, a, p->samples_per_unit, stats != nullptr, stream, progress ? &pr : nullptr)) return rc;
-  hipEvent_t done;
-  HIP_TRY(hipEventCreateWithFlags(&done, hipEventDisableTiming), "hipEventCreate");
-  std::unique_ptr<std::remove_pointer<hipEvent_t>::type, decltype(&hipEventDestroy)> hold3(done, &hipEventDestroy);
+  Event done;
+  HIP_TRY(done.create(), "hipEventCreate");
   HIP_TRY(hipEventRecord(done, stream), "hipEventRecord");
   if (int rc = wait_with_progress({done}, {s->device}, {&pr}, pr.pixels, progress, user)) return rc;
   HIP_TRY(hipMemcpyAsync(host_out, d_out, bytes, hipMemcpyDeviceToHost, stream), "copy output");
@@ -1176,16 +1085,13 @@ int yart_finalize_rgba8(int device, const double* xyz, uint32_t w, uint32_t h, u
   if (!xyz || !rgba || !w || !h) return fail(YART_ERR_INVALID, "bad argument");
   DeviceGuard g(device);
   const size_t n = (size_t)w * h;
-  double* dx = nullptr;
-  uint8_t* dr = nullptr;
-  HIP_TRY(hipMalloc(&dx, sizeof(double) * 3 * n), "hipMalloc");
-  std::unique_ptr<double, decltype(&hipFree)> h1(dx, &hipFree);
-  HIP_TRY(hipMalloc(&dr, 4 * n), "hipMalloc");
-  std::unique_ptr<uint8_t, decltype(&hipFree)> h2(dr, &hipFree);
-  HIP_TRY(hipMemcpy(dx, xyz, sizeof(double) * 3 * n, hipMemcpyHostToDevice), "copy in");
-  HIP_TRY(launch_finalize(dx, w, h, spp, dr, nullptr), "launch k_finalize");
+  DevBuf dx, dr;
+  HIP_TRY(dx.alloc(sizeof(double) * 3 * n), "hipMalloc");
+  HIP_TRY(dr.alloc(4 * n), "hipMalloc");
+  HIP_TRY(hipMemcpy(dx.get<void>(), xyz, sizeof(double) * 3 * n, hipMemcpyHostToDevice), "copy in");
+  HIP_TRY(launch_finalize(dx.get<double>(), w, h, spp, dr.get<uint8_t>(), nullptr), "launch k_finalize");
   HIP_TRY(hipStreamSynchronize(nullptr), "k_finalize");
-  HIP_TRY(hipMemcpy(rgba, dr, 4 * n, hipMemcpyDeviceToHost), "copy out");
+  HIP_TRY(hipMemcpy(rgba, dr.get<void>(), 4 * n, hipMemcpyDeviceToHost), "copy out");
   return ok();
 }
 
@@ -1193,24 +1099,17 @@ int yart_intersect(yart_scene* s, const double* rays, uint32_t n, double* hits, 
   if (!s || (n && (!rays || !hits || !obj))) return fail(YART_ERR_INVALID, "null argument");
   if (n == 0) return ok();
   DeviceGuard g(s->device);
-  hipStream_t st;
-  if (int rc = acquire_stream(s, &st)) return rc;
-  struct Release {
-    yart_scene* s; hipStream_t st;
-    ~Release() { (void)hipStreamSynchronize(st); release_stream(s, st); }
-  } release{s, st};
-  double *dr = nullptr, *dh = nullptr;
-  int32_t* dobj = nullptr;
-  HIP_TRY(hipMalloc(&dr, sizeof(double) * 8 * (size_t)n), "hipMalloc");
-  std::unique_ptr<double, decltype(&hipFree)> h1(dr, &hipFree);
-  HIP_TRY(hipMalloc(&dh, sizeof(double) * 8 * (size_t)n), "hipMalloc");
-  std::unique_ptr<double, decltype(&hipFree)> h2(dh, &hipFree);
-  HIP_TRY(hipMalloc(&dobj, sizeof(int32_t) * (size_t)n), "hipMalloc");
-  std::unique_ptr<int32_t, decltype(&hipFree)> h3(dobj, &hipFree);
-  HIP_TRY(hipMemcpyAsync(dr, rays, sizeof(double) * 8 * (size_t)n, hipMemcpyHostToDevice, st), "copy rays");
-  HIP_TRY(launch_intersect(s->dev, dr, n, dh, dobj, st), "launch k_intersect");
-  HIP_TRY(hipMemcpyAsync(hits, dh, sizeof(double) * 8 * (size_t)n, hipMemcpyDeviceToHost, st), "copy hits");
-  HIP_TRY(hipMemcpyAsync(obj, dobj, sizeof(int32_t) * (size_t)n, hipMemcpyDeviceToHost, st), "copy obj");
+  StreamLease st(s);
+  if (int rc = st.acquire()) return rc;
+  const size_t ray_bytes = sizeof(double) * 8 * (size_t)n, obj_bytes = sizeof(int32_t) * (size_t)n;
+  DevBuf dr, dh, dobj;
+  HIP_TRY(dr.alloc(ray_bytes), "hipMalloc");
+  HIP_TRY(dh.alloc(ray_bytes), "hipMalloc");
+  HIP_TRY(dobj.alloc(obj_bytes), "hipMalloc");
+  HIP_TRY(hipMemcpyAsync(dr.get<void>(), rays, ray_bytes, hipMemcpyHostToDevice, st), "copy rays");
+  HIP_TRY(launch_intersect(s->dev, dr.get<double>(), n, dh.get<double>(), dobj.get<int32_t>(), st), "launch k_intersect");
+  HIP_TRY(hipMemcpyAsync(hits, dh.get<void>(), ray_bytes, hipMemcpyDeviceToHost, st), "copy hits");
+  HIP_TRY(hipMemcpyAsync(obj, dobj.get<void>(), obj_bytes, hipMemcpyDeviceToHost, st), "copy obj");
   HIP_TRY(hipStreamSynchronize(st), "k_intersect");
   return ok();
 }
@@ -1218,30 +1117,26 @@ int yart_intersect(yart_scene* s, const double* rays, uint32_t n, double* hits, 
 int yart_probe_rng(int device, uint64_t seed, uint32_t pixel, uint32_t sample, uint32_t n, double* out) {
   if (!out || n == 0) return fail(YART_ERR_INVALID, "bad argument");
   DeviceGuard g(device);
-  double* d = nullptr;
-  HIP_TRY(hipMalloc(&d, sizeof(double) * n), "hipMalloc");
-  std::unique_ptr<double, decltype(&hipFree)> h(d, &hipFree);
-  HIP_TRY(launch_probe_rng(seed, pixel, sample, n, d, nullptr), "launch k_probe_rng");
+  DevBuf d;
+  HIP_TRY(d.alloc(sizeof(double) * n), "hipMalloc");
+  HIP_TRY(launch_probe_rng(seed, pixel, sample, n, d.get<double>(), nullptr), "launch k_probe_rng");
   HIP_TRY(hipStreamSynchronize(nullptr), "k_probe_rng");
-  HIP_TRY(hipMemcpy(out, d, sizeof(double) * n, hipMemcpyDeviceToHost), "copy");
+  HIP_TRY(hipMemcpy(out, d.get<void>(), sizeof(double) * n, hipMemcpyDeviceToHost), "copy");
   return ok();
 }
 
 int yart_probe_math(int device, int op, const double* a, const double* b, uint32_t n, double* out) {
   if (!a || !out || n == 0 || ((op == 1 || op == 4) && !b)) return fail(YART_ERR_INVALID, "bad argument");
   DeviceGuard g(device);
-  double *da = nullptr, *db = nullptr, *dout = nullptr;
-  HIP_TRY(hipMalloc(&da, sizeof(double) * n), "hipMalloc");
-  std::unique_ptr<double, decltype(&hipFree)> h1(da, &hipFree);
-  HIP_TRY(hipMalloc(&db, sizeof(double) * n), "hipMalloc");
-  std::unique_ptr<double, decltype(&hipFree)> h2(db, &hipFree);
-  HIP_TRY(hipMalloc(&dout, sizeof(double) * n), "hipMalloc");
-  std::unique_ptr<double, decltype(&hipFree)> h3(dout, &hipFree);
-  HIP_TRY(hipMemcpy(da, a, sizeof(double) * n, hipMemcpyHostToDevice), "copy a");
-  HIP_TRY(hipMemcpy(db, b ? b : a, sizeof(double) * n, hipMemcpyHostToDevice), "copy b");
-  HIP_TRY(launch_probe_math(op, da, db, n, dout, nullptr), "launch k_probe_math");
+  DevBuf da, db, dout;
+  HIP_TRY(da.alloc(sizeof(double) * n), "hipMalloc");
+  HIP_TRY(db.alloc(sizeof(double) * n), "hipMalloc");
+  HIP_TRY(dout.alloc(sizeof(double) * n), "hipMalloc");
+  HIP_TRY(hipMemcpy(da.get<void>(), a, sizeof(double) * n, hipMemcpyHostToDevice), "copy a");
+  HIP_TRY(hipMemcpy(db.get<void>(), b ? b : a, sizeof(double) * n, hipMemcpyHostToDevice), "copy b");
+  HIP_TRY(launch_probe_math(op, da.get<double>(), db.get<double>(), n, dout.get<double>(), nullptr), "launch k_probe_math");
   HIP_TRY(hipStreamSynchronize(nullptr), "k_probe_math");
-  HIP_TRY(hipMemcpy(out, dout, sizeof(double) * n, hipMemcpyDeviceToHost), "copy out");
+  HIP_TRY(hipMemcpy(out, dout.get<void>(), sizeof(double) * n, hipMemcpyDeviceToHost), "copy out");
   return ok();
 }
 

@@ -29,11 +29,9 @@ using namespace yart_impl;
 struct yart_comm {
   ncclComm_t comm = nullptr;
   int device = 0, rank = 0, n_ranks = 1;
-  // root-side receive buffer (n_ranks packets) and send staging, grown on demand
-  double* recv = nullptr;
-  size_t recv_bytes = 0;
+  DevBuf recv;  // root-side receive buffer (n_ranks packets), grown on demand
   ~yart_comm() {
-    if (recv) { (void)hipSetDevice(device); (void)hipFree(recv); }
+    if (recv) { (void)hipSetDevice(device); (void)recv.release(); }
     if (comm) (void)ncclCommDestroy(comm);
   }
 };
@@ -53,23 +51,15 @@ uint64_t packet_len(uint32_t w, uint32_t h, uint32_t n) {  // doubles per rank: 
   return yart_shard_packed_len(w, h, 0, n);
 }
 
-int ensure_recv(yart_comm* c, size_t bytes) {
-  if (c->recv_bytes >= bytes) return YART_OK;
-  if (c->recv) HIP_TRY(hipFree(c->recv), "hipFree");
-  c->recv = nullptr; c->recv_bytes = 0;
-  HIP_TRY(hipMalloc(&c->recv, bytes), "hipMalloc gather buffer");
-  c->recv_bytes = bytes;
-  return YART_OK;
-}
-
 // The gather of one rank (inside a group for single-process communicators). Packets are equal
 // sized (ncclGather's contract): a shard with fewer blocks sends the tail of its buffer too, which
 // the unpack never reads. The send buffer must therefore hold packet_len doubles.
 int enqueue_gather(yart_comm* c, const double* d_packed, uint32_t w, uint32_t h, int root, hipStream_t st) {
   const uint64_t n = packet_len(w, h, (uint32_t)c->n_ranks);
-  if (c->rank == root)
-    if (int rc = ensure_recv(c, sizeof(double) * n * (size_t)c->n_ranks)) return rc;
-  NCCL_TRY(ncclGather(d_packed, c->rank == root ? c->recv : nullptr, n, ncclFloat64, root, c->comm, st), "ncclGather");
+  // no stream to drain: the release of the old buffer waits for the device
+  if (c->rank == root) HIP_TRY(c->recv.reserve(sizeof(double) * n * (size_t)c->n_ranks, {}), "hipMalloc gather buffer");
+  NCCL_TRY(ncclGather(d_packed, c->rank == root ? c->recv.get<double>() : nullptr, n, ncclFloat64, root, c->comm, st),
+           "ncclGather");
   return YART_OK;
 }
 
@@ -123,8 +113,8 @@ int yart_gather_frame_async(yart_comm* c, const double* d_packed, uint32_t w, ui
   hipStream_t st = (hipStream_t)stream;
   if (int rc = enqueue_gather(c, d_packed, w, h, root, st)) return rc;
   if (c->rank == root)
-    HIP_TRY(launch_unpack_shards(c->recv, (uint32_t)c->n_ranks, packet_len(w, h, (uint32_t)c->n_ranks), w, h, d_frame, st),
-            "launch k_unpack_shards");
+    HIP_TRY(launch_unpack_shards(c->recv.get<double>(), (uint32_t)c->n_ranks, packet_len(w, h, (uint32_t)c->n_ranks), w, h,
+                                 d_frame, st), "launch k_unpack_shards");
   return ok();
 }
 
@@ -137,23 +127,24 @@ int yart_gather_frame_async(yart_comm* c, const double* d_packed, uint32_t w, ui
 // overlap (the next frame's renders take the SIMD slots the previous frame's drain leaves idle);
 // the gathers still run in submission order on every device (each waits for the previous
 // submission's gather on its device), which is the order RCCL needs on a communicator.
+struct SlotDevice {    // a slot's part on one device
+  Stream stream;       // library-owned, non-blocking
+  DevBuf packed;       // packet_len doubles
+  Event gathered;      // its ncclGather of the latest frame
+  Event rendered;      // its render of the latest frame (yart_multi_query)
+  // its ncclGather's interval (from its launch, after its render and the previous submission's
+  // gather, to its end) for each frame not yet read — the per-device balance of the first N-GPU
+  // runs (which device waited in the gather for which)
+  std::vector<EventPool::Lease> gather_events;
+};
 struct MultiSlot {
-  std::vector<hipStream_t> streams;   // per device, library-owned, non-blocking
-  std::vector<double*> packed;        // per device, packet_len doubles
-  std::vector<size_t> packed_bytes;
-  std::vector<hipEvent_t> gathered;   // per device: its ncclGather of the latest frame
-  std::vector<hipEvent_t> rendered;   // per device: its render of the latest frame (yart_multi_query)
-  hipEvent_t start = nullptr;         // devices[0]: the caller stream's work before the frame
-  hipEvent_t done = nullptr;          // devices[0]: the frame unpacked
-  double* recv = nullptr;             // devices[0]: every shard's packet
-  size_t recv_bytes = 0;
+  std::vector<SlotDevice> dev;
+  Event start;         // devices[0]: the caller stream's work before the frame
+  Event done;          // devices[0]: the frame unpacked
+  DevBuf recv;         // devices[0]: every shard's packet
   // devices[0]: the root's gather + unpack interval of each frame not yet read (timing)
-  std::vector<std::pair<hipEvent_t, hipEvent_t>> gather_events;
-  // per device: its ncclGather's interval (from its launch, after its render and the previous
-  // submission's gather, to its end) for each frame not yet read — the per-device balance of the
-  // first N-GPU runs (which device waited in the gather for which)
-  std::vector<std::vector<std::pair<hipEvent_t, hipEvent_t>>> dev_gather_events;
-  uint64_t last_use = 0;              // submission number of its latest frame (eviction order)
+  std::vector<EventPool::Lease> gather_events;
+  uint64_t last_use = 0;  // submission number of its latest frame (eviction order)
 };
 
 struct yart_multi {
@@ -162,15 +153,16 @@ struct yart_multi {
   std::vector<yart_scene*> scenes;
   std::vector<yart_comm*> comms;
   std::mutex mu;                                   // submissions are enqueued one at a time
+  // recycled pairs of timing events, of devices[0] and per device (before the slots, whose leases
+  // return into them)
+  EventPool gather_pool;
+  std::vector<EventPool> dev_pool;
   std::map<hipStream_t, std::unique_ptr<MultiSlot>> slots;  // by caller stream (devices[0]), at most kMaxSlots
   uint64_t submissions = 0;
   MultiSlot* latest = nullptr;  // the slot of the latest submission (yart_multi_query)
   std::vector<hipEvent_t> last_gather;             // per device: the latest submission's gather
-  hipStream_t host_stream = nullptr;               // devices[0]: yart_render_multi's caller stream
-  double* frame = nullptr;                         // devices[0]: yart_render_multi's frame
-  size_t frame_bytes = 0;
-  std::vector<std::pair<hipEvent_t, hipEvent_t>> gather_pool;  // devices[0]: recycled timing pairs
-  std::vector<std::vector<std::pair<hipEvent_t, hipEvent_t>>> dev_pool;  // per device: recycled timing pairs
+  Stream host_stream;                              // devices[0]: yart_render_multi's caller stream
+  DevBuf frame;                                    // devices[0]: yart_render_multi's frame
   double render_ms = 0.0, gather_ms = 0.0;  // yart_render_multi's last frame
   // per device, summed over the frames of the latest timing read (yart_multi_frame_timing or
   // yart_render_multi): render-kernel time and its own gather time (yart_multi_device_timing)
@@ -180,47 +172,34 @@ struct yart_multi {
   // used slot when a new caller stream would exceed kMaxSlots, so a caller that makes a stream per
   // frame does not grow device memory without bound — ADVICE r03).
   void release_slot(MultiSlot& s) {
-    for (int d = 0; d < n && d < (int)devices.size(); ++d) {
-      (void)hipSetDevice(devices[(size_t)d]);
-      if ((size_t)d < s.streams.size() && s.streams[(size_t)d]) (void)hipStreamSynchronize(s.streams[(size_t)d]);
+    for (size_t d = 0; d < s.dev.size(); ++d) {
+      (void)hipSetDevice(devices[d]);
+      (void)hipStreamSynchronize(s.dev[d].stream);
     }
-    for (int d = 0; d < n && d < (int)devices.size(); ++d) {
-      (void)hipSetDevice(devices[(size_t)d]);
+    // each device's part goes while that device is current, the last device first: devices[0] is
+    // then current for the root's part, which goes with the rest of the slot
+    while (!s.dev.empty()) {
+      const size_t d = s.dev.size() - 1;
+      (void)hipSetDevice(devices[d]);
       // the scene's unread frame-timing events of this stream: read and recycled now, or a later
       // stream that happens to get the same handle would report these frames as its own
-      if ((size_t)d < s.streams.size() && s.streams[(size_t)d] && (size_t)d < scenes.size()) {
-        double r = 0.0, a = 0.0;
-        uint32_t f = 0;
-        (void)yart_frame_timing(scenes[(size_t)d], s.streams[(size_t)d], &r, &a, &f);
-      }
-      if ((size_t)d < s.packed.size() && s.packed[(size_t)d]) (void)hipFree(s.packed[(size_t)d]);
-      if ((size_t)d < s.gathered.size() && s.gathered[(size_t)d]) (void)hipEventDestroy(s.gathered[(size_t)d]);
-      if ((size_t)d < s.rendered.size() && s.rendered[(size_t)d]) (void)hipEventDestroy(s.rendered[(size_t)d]);
-      if ((size_t)d < s.streams.size() && s.streams[(size_t)d]) (void)hipStreamDestroy(s.streams[(size_t)d]);
-      if ((size_t)d < s.dev_gather_events.size() && (size_t)d < dev_pool.size())
-        for (auto& e : s.dev_gather_events[(size_t)d]) dev_pool[(size_t)d].push_back(e);  // unread: dropped
-      if (d == 0) {
-        for (auto& e : s.gather_events) gather_pool.push_back(e);  // unread timings are dropped
-        s.gather_events.clear();
-        if (s.recv) (void)hipFree(s.recv);
-        if (s.start) (void)hipEventDestroy(s.start);
-        if (s.done) (void)hipEventDestroy(s.done);
-      }
+      double r = 0.0, a = 0.0;
+      uint32_t f = 0;
+      (void)yart_frame_timing(scenes[d], s.dev[d].stream, &r, &a, &f);
+      s.dev.pop_back();  // unread gather timings are dropped: their events return to the pools
     }
     s = MultiSlot{};
   }
   ~yart_multi() {
     for (auto& kv : slots) release_slot(*kv.second);
-    for (int d = 0; d < n && d < (int)devices.size(); ++d) {
-      (void)hipSetDevice(devices[(size_t)d]);
-      if ((size_t)d < dev_pool.size())
-        for (auto& e : dev_pool[(size_t)d]) { (void)hipEventDestroy(e.first); (void)hipEventDestroy(e.second); }
-      if (d == 0) {
-        for (auto& e : gather_pool) { (void)hipEventDestroy(e.first); (void)hipEventDestroy(e.second); }
-        if (frame) (void)hipFree(frame);
-        if (host_stream) { (void)hipStreamSynchronize(host_stream); (void)hipStreamDestroy(host_stream); }
-      }
+    for (size_t d = devices.size(); d-- > 0;) {  // devices[0] last: current for the root's members below
+      (void)hipSetDevice(devices[d]);
+      dev_pool[d].clear();
     }
+    gather_pool.clear();
+    (void)frame.release();
+    if (host_stream) (void)hipStreamSynchronize(host_stream);
+    host_stream.reset();
     for (yart_comm* c : comms) delete c;
     for (yart_scene* s : scenes) yart_scene_destroy(s);
   }
@@ -239,49 +218,35 @@ struct RestoreDevice {
 // recently used slot, after that slot's frames have finished (its streams are drained).
 constexpr size_t kMaxSlots = 8;
 int multi_slot(yart_multi* m, hipStream_t caller, MultiSlot** out) {
-  if (!m->slots.count(caller) && m->slots.size() >= kMaxSlots) {
-    auto lru = m->slots.begin();
-    for (auto it = m->slots.begin(); it != m->slots.end(); ++it)
-      if (it->second->last_use < lru->second->last_use) lru = it;
-    if (m->latest == lru->second.get()) m->latest = nullptr;
-    m->release_slot(*lru->second);
-    m->slots.erase(lru);
-  }
-  auto& e = m->slots[caller];
-  if (!e) {
+  auto it = m->slots.find(caller);
+  if (it == m->slots.end()) {
+    if (m->slots.size() >= kMaxSlots) {
+      auto lru = m->slots.begin();
+      for (auto i = m->slots.begin(); i != m->slots.end(); ++i)
+        if (i->second->last_use < lru->second->last_use) lru = i;
+      if (m->latest == lru->second.get()) m->latest = nullptr;
+      m->release_slot(*lru->second);
+      m->slots.erase(lru);
+    }
+    // built completely before it joins the map: a failure leaves no entry behind, and what was made
+    // so far goes with `s`
     auto s = std::make_unique<MultiSlot>();
-    s->streams.assign((size_t)m->n, nullptr);
-    s->packed.assign((size_t)m->n, nullptr);
-    s->packed_bytes.assign((size_t)m->n, 0);
-    s->gathered.assign((size_t)m->n, nullptr);
-    s->rendered.assign((size_t)m->n, nullptr);
-    s->dev_gather_events.assign((size_t)m->n, {});
+    s->dev.resize((size_t)m->n);
     for (int d = 0; d < m->n; ++d) {
+      SlotDevice& D = s->dev[(size_t)d];
       HIP_TRY(hipSetDevice(m->devices[(size_t)d]), "hipSetDevice");
-      HIP_TRY(hipStreamCreateWithFlags(&s->streams[(size_t)d], hipStreamNonBlocking), "hipStreamCreate");
-      HIP_TRY(hipEventCreateWithFlags(&s->gathered[(size_t)d], hipEventDisableTiming), "hipEventCreate");
-      HIP_TRY(hipEventCreateWithFlags(&s->rendered[(size_t)d], hipEventDisableTiming), "hipEventCreate");
+      HIP_TRY(D.stream.create(), "hipStreamCreate");
+      HIP_TRY(D.gathered.create(), "hipEventCreate");
+      HIP_TRY(D.rendered.create(), "hipEventCreate");
       if (d == 0) {
-        HIP_TRY(hipEventCreateWithFlags(&s->start, hipEventDisableTiming), "hipEventCreate");
-        HIP_TRY(hipEventCreateWithFlags(&s->done, hipEventDisableTiming), "hipEventCreate");
+        HIP_TRY(s->start.create(), "hipEventCreate");
+        HIP_TRY(s->done.create(), "hipEventCreate");
       }
     }
-    e = std::move(s);
+    it = m->slots.emplace(caller, std::move(s)).first;
   }
-  e->last_use = ++m->submissions;
-  *out = e.get();
-  return YART_OK;
-}
-
-// A pair of timing events from `pool` (recycled) or new ones, on the current device.
-int event_pair(std::vector<std::pair<hipEvent_t, hipEvent_t>>& pool, std::pair<hipEvent_t, hipEvent_t>& out) {
-  if (!pool.empty()) {
-    out = pool.back();
-    pool.pop_back();
-    return YART_OK;
-  }
-  HIP_TRY(hipEventCreate(&out.first), "hipEventCreate");
-  if (hipError_t e = hipEventCreate(&out.second)) { (void)hipEventDestroy(out.first); return hip_fail(e, "hipEventCreate"); }
+  it->second->last_use = ++m->submissions;
+  *out = it->second.get();
   return YART_OK;
 }
 
@@ -309,27 +274,22 @@ int multi_submit(yart_multi* m, const yart_camera* cam, const yart_render_params
   auto render_one = [&](int d) -> int {
     const size_t di = (size_t)d;
     HIP_TRY(hipSetDevice(m->devices[di]), "hipSetDevice");
-    hipStream_t st = S->streams[di];
-    if (S->packed_bytes[di] < pk_bytes) {
-      if (S->packed[di]) {
-        HIP_TRY(hipStreamSynchronize(st), "drain");
-        HIP_TRY(hipFree(S->packed[di]), "hipFree");
-      }
-      S->packed[di] = nullptr; S->packed_bytes[di] = 0;
-      HIP_TRY(hipMalloc(&S->packed[di], pk_bytes), "hipMalloc packed shard");
+    SlotDevice& D = S->dev[di];
+    hipStream_t st = D.stream;
+    if (D.packed.bytes() < pk_bytes) {
+      HIP_TRY(D.packed.reserve(pk_bytes, {st}), "hipMalloc packed shard");
       // a smaller shard sends its tail too (equal-sized packets); zeroed once, never read
-      HIP_TRY(hipMemsetAsync(S->packed[di], 0, pk_bytes, st), "hipMemset");
-      S->packed_bytes[di] = pk_bytes;
+      HIP_TRY(hipMemsetAsync(D.packed.get<void>(), 0, pk_bytes, st), "hipMemset");
     }
     RenderArgs a;
     yart_render_params q = *p;
     q.shard_index = (uint32_t)d;
     q.shard_count = (uint32_t)n;
-    if (int rc = make_args(m->scenes[di], cam, &q, S->packed[di], a)) return rc;
+    if (int rc = make_args(m->scenes[di], cam, &q, D.packed.get<double>(), a)) return rc;
     a.packed = 1;
     Progress* pr = prog ? &(*prog)[di] : nullptr;
     if (int rc = launch_frame(m->scenes[di], a, p->samples_per_unit, false, st, pr)) return rc;
-    HIP_TRY(hipEventRecord(S->rendered[di], st), "hipEventRecord");
+    HIP_TRY(hipEventRecord(D.rendered, st), "hipEventRecord");
     return YART_OK;
   };
   if (n > 1 && m->scenes[0]->wavefront) {
@@ -356,73 +316,67 @@ int multi_submit(yart_multi* m, const yart_camera* cam, const yart_render_params
   }
   // 2. the root's receive buffer (per slot: a later slot's gather may land while this one unpacks)
   HIP_TRY(hipSetDevice(m->devices[0]), "hipSetDevice");
-  if (S->recv_bytes < pk_bytes * (size_t)n) {
-    if (S->recv) {
-      HIP_TRY(hipStreamSynchronize(S->streams[0]), "drain");
-      HIP_TRY(hipFree(S->recv), "hipFree");
-    }
-    S->recv = nullptr; S->recv_bytes = 0;
-    HIP_TRY(hipMalloc(&S->recv, pk_bytes * (size_t)n), "hipMalloc gather buffer");
-    S->recv_bytes = pk_bytes * (size_t)n;
-  }
-  // The frame's timing pairs join the slot's lists only once both ends are recorded (below): a
-  // submission that fails half way returns them to their pools instead of leaving a pair that
-  // multi_timing cannot read.
-  std::pair<hipEvent_t, hipEvent_t> gev;
-  if (int rc = event_pair(m->gather_pool, gev)) return rc;
-  std::vector<std::pair<hipEvent_t, hipEvent_t>> dev_ev;
-  dev_ev.reserve((size_t)n);
-  struct Pending {
-    yart_multi* m;
-    std::pair<hipEvent_t, hipEvent_t>& gev;
-    std::vector<std::pair<hipEvent_t, hipEvent_t>>& dev_ev;
-    bool handed_over = false;
-    ~Pending() {
-      if (handed_over) return;
-      m->gather_pool.push_back(gev);
-      for (size_t d = 0; d < dev_ev.size(); ++d) m->dev_pool[d].push_back(dev_ev[d]);
-    }
-  } pending{m, gev, dev_ev};
+  HIP_TRY(S->recv.reserve(pk_bytes * (size_t)n, {S->dev[0].stream}), "hipMalloc gather buffer");
+  // The frame's timing pairs are leases until both ends are recorded and join the slot's lists
+  // only then (below): a submission that fails half way returns them to their pools instead of
+  // leaving a pair that multi_timing cannot read.
+  EventPool::Lease gev;
+  HIP_TRY(m->gather_pool.take(2, gev), "hipEventCreate");
+  std::vector<EventPool::Lease> dev_ev((size_t)n);
   // 3. ONE gather to devices[0], each device's part right behind its render; in submission order
   for (int d = 0; d < n; ++d) {
     const size_t di = (size_t)d;
+    SlotDevice& D = S->dev[di];
     HIP_TRY(hipSetDevice(m->devices[di]), "hipSetDevice");
-    if (m->last_gather[di] && m->last_gather[di] != S->gathered[di])
-      HIP_TRY(hipStreamWaitEvent(S->streams[di], m->last_gather[di], 0), "hipStreamWaitEvent");
-    if (d == 0) HIP_TRY(hipEventRecord(gev.first, S->streams[0]), "hipEventRecord");
-    std::pair<hipEvent_t, hipEvent_t> pr;
-    if (int rc = event_pair(m->dev_pool[di], pr)) return rc;
-    dev_ev.push_back(pr);
-    HIP_TRY(hipEventRecord(pr.first, S->streams[di]), "hipEventRecord");
+    if (m->last_gather[di] && m->last_gather[di] != D.gathered)
+      HIP_TRY(hipStreamWaitEvent(D.stream, m->last_gather[di], 0), "hipStreamWaitEvent");
+    if (d == 0) HIP_TRY(hipEventRecord(gev[0], D.stream), "hipEventRecord");
+    HIP_TRY(m->dev_pool[di].take(2, dev_ev[di]), "hipEventCreate");
+    HIP_TRY(hipEventRecord(dev_ev[di][0], D.stream), "hipEventRecord");
   }
   NCCL_TRY(ncclGroupStart(), "ncclGroupStart");
   for (int d = 0; d < n; ++d) {
     const size_t di = (size_t)d;
     (void)hipSetDevice(m->devices[di]);
-    ncclResult_t r = ncclGather(S->packed[di], d == 0 ? S->recv : nullptr, stride, ncclFloat64, 0, m->comms[di]->comm,
-                                S->streams[di]);
+    ncclResult_t r = ncclGather(S->dev[di].packed.get<double>(), d == 0 ? S->recv.get<double>() : nullptr, stride,
+                                ncclFloat64, 0, m->comms[di]->comm, S->dev[di].stream);
     if (r != ncclSuccess) { (void)ncclGroupEnd(); return nccl_fail(r, "ncclGather"); }
   }
   NCCL_TRY(ncclGroupEnd(), "ncclGroupEnd");
   for (int d = 0; d < n; ++d) {
     const size_t di = (size_t)d;
+    SlotDevice& D = S->dev[di];
     HIP_TRY(hipSetDevice(m->devices[di]), "hipSetDevice");
-    HIP_TRY(hipEventRecord(dev_ev[di].second, S->streams[di]), "hipEventRecord");
-    HIP_TRY(hipEventRecord(S->gathered[di], S->streams[di]), "hipEventRecord");
-    m->last_gather[di] = S->gathered[di];
+    HIP_TRY(hipEventRecord(dev_ev[di][1], D.stream), "hipEventRecord");
+    HIP_TRY(hipEventRecord(D.gathered, D.stream), "hipEventRecord");
+    m->last_gather[di] = D.gathered;
   }
   // 4. unpack on the root, after whatever the caller stream had queued (it may still read d_frame)
+  const hipStream_t root = S->dev[0].stream;
   HIP_TRY(hipSetDevice(m->devices[0]), "hipSetDevice");
   HIP_TRY(hipEventRecord(S->start, caller), "hipEventRecord");
-  HIP_TRY(hipStreamWaitEvent(S->streams[0], S->start, 0), "hipStreamWaitEvent");
-  HIP_TRY(launch_unpack_shards(S->recv, (uint32_t)n, stride, W, H, d_frame, S->streams[0]), "launch k_unpack_shards");
-  HIP_TRY(hipEventRecord(gev.second, S->streams[0]), "hipEventRecord");
-  S->gather_events.push_back(gev);
-  for (int d = 0; d < n; ++d) S->dev_gather_events[(size_t)d].push_back(dev_ev[(size_t)d]);
-  pending.handed_over = true;
-  HIP_TRY(hipEventRecord(S->done, S->streams[0]), "hipEventRecord");
+  HIP_TRY(hipStreamWaitEvent(root, S->start, 0), "hipStreamWaitEvent");
+  HIP_TRY(launch_unpack_shards(S->recv.get<double>(), (uint32_t)n, stride, W, H, d_frame, root), "launch k_unpack_shards");
+  HIP_TRY(hipEventRecord(gev[1], root), "hipEventRecord");
+  S->gather_events.push_back(std::move(gev));  // both ends recorded: handed over
+  for (int d = 0; d < n; ++d) S->dev[(size_t)d].gather_events.push_back(std::move(dev_ev[(size_t)d]));
+  HIP_TRY(hipEventRecord(S->done, root), "hipEventRecord");
   HIP_TRY(hipStreamWaitEvent(caller, S->done, 0), "hipStreamWaitEvent");
   return YART_OK;
+}
+
+// The summed intervals of a slot's timing pairs (on the current device). The pairs are taken out of
+// the slot first and recycled whatever happens: a failed read does not leave pairs behind for every
+// later call to trip over.
+hipError_t sum_pairs(std::vector<EventPool::Lease>& pairs, double& sum) {
+  std::vector<EventPool::Lease> evs;
+  evs.swap(pairs);
+  hipError_t bad = hipSuccess;
+  for (auto& e : evs) {
+    float ms = 0.0f;
+    if (bad == hipSuccess && (bad = hipEventElapsedTime(&ms, e[0], e[1])) == hipSuccess) sum += ms;
+  }
+  return bad;
 }
 
 // Summed kernel times of the frames submitted since the last read, over every slot or one
@@ -440,24 +394,14 @@ int multi_timing(yart_multi* m, MultiSlot* only, double* render_ms, double* gath
     double r = 0.0, dg = 0.0;
     for (auto& kv : m->slots) {
       if (only && kv.second.get() != only) continue;
+      SlotDevice& D = kv.second->dev[(size_t)d];
       double rr = 0.0, acc = 0.0;
       uint32_t f = 0;
-      if (int rc = yart_frame_timing(m->scenes[(size_t)d], kv.second->streams[(size_t)d], &rr, &acc, &f)) return rc;
+      if (int rc = yart_frame_timing(m->scenes[(size_t)d], D.stream, &rr, &acc, &f)) return rc;
       r += rr;
       if (d == 0) nf += f;
       HIP_TRY(hipSetDevice(m->devices[(size_t)d]), "hipSetDevice");
-      // taken out of the slot first and recycled whatever happens: a failed read does not leave
-      // pairs behind for every later call to trip over
-      std::vector<std::pair<hipEvent_t, hipEvent_t>> evs;
-      evs.swap(kv.second->dev_gather_events[(size_t)d]);
-      hipError_t bad = hipSuccess;
-      for (auto& e : evs) {
-        float ms = 0.0f;
-        if (bad == hipSuccess) bad = hipEventElapsedTime(&ms, e.first, e.second);
-        if (bad == hipSuccess) dg += ms;
-        m->dev_pool[(size_t)d].push_back(e);
-      }
-      if (bad != hipSuccess) return hip_fail(bad, "hipEventElapsedTime");
+      HIP_TRY(sum_pairs(D.gather_events, dg), "hipEventElapsedTime");
     }
     m->dev_render_ms[(size_t)d] = r;
     m->dev_gather_ms[(size_t)d] = dg;
@@ -466,19 +410,8 @@ int multi_timing(yart_multi* m, MultiSlot* only, double* render_ms, double* gath
   m->dev_frames = nf;
   HIP_TRY(hipSetDevice(m->devices[0]), "hipSetDevice");
   double g = 0.0;
-  for (auto& kv : m->slots) {
-    if (only && kv.second.get() != only) continue;
-    std::vector<std::pair<hipEvent_t, hipEvent_t>> evs;
-    evs.swap(kv.second->gather_events);
-    hipError_t bad = hipSuccess;
-    for (auto& e : evs) {
-      float ms = 0.0f;
-      if (bad == hipSuccess) bad = hipEventElapsedTime(&ms, e.first, e.second);
-      if (bad == hipSuccess) g += ms;
-      m->gather_pool.push_back(e);
-    }
-    if (bad != hipSuccess) return hip_fail(bad, "hipEventElapsedTime");
-  }
+  for (auto& kv : m->slots)
+    if (!only || kv.second.get() == only) HIP_TRY(sum_pairs(kv.second->gather_events, g), "hipEventElapsedTime");
   *render_ms = worst;
   *gather_ms = g;
   *frames = nf;
@@ -502,7 +435,7 @@ int yart_multi_create(int n, const int* devices, const yart_scene_desc* desc, ya
   m->n = n;
   m->devices.assign(devices, devices + n);
   m->last_gather.assign((size_t)n, nullptr);
-  m->dev_pool.assign((size_t)n, {});
+  m->dev_pool = std::vector<EventPool>((size_t)n);
   RestoreDevice restore;
   for (int d = 0; d < n; ++d) {  // the scene is uploaded once per device, here
     yart_scene* s = nullptr;
@@ -510,7 +443,7 @@ int yart_multi_create(int n, const int* devices, const yart_scene_desc* desc, ya
     m->scenes.push_back(s);
   }
   HIP_TRY(hipSetDevice(devices[0]), "hipSetDevice");
-  HIP_TRY(hipStreamCreateWithFlags(&m->host_stream, hipStreamNonBlocking), "hipStreamCreate");
+  HIP_TRY(m->host_stream.create(), "hipStreamCreate");
   m->comms.assign((size_t)n, nullptr);
   if (int rc = yart_comm_init_all(n, devices, m->comms.data())) return rc;
   *out = m.release();
@@ -542,17 +475,9 @@ int yart_render_multi(yart_multi* m, const yart_camera* cam, const yart_render_p
   RestoreDevice restore;
   HIP_TRY(hipSetDevice(m->devices[0]), "hipSetDevice");
   hipStream_t hs = m->host_stream;
-  if (m->frame_bytes < frame_bytes) {
-    if (m->frame) {
-      HIP_TRY(hipStreamSynchronize(hs), "drain");
-      HIP_TRY(hipFree(m->frame), "hipFree");
-    }
-    m->frame = nullptr; m->frame_bytes = 0;
-    HIP_TRY(hipMalloc(&m->frame, frame_bytes), "hipMalloc frame");
-    m->frame_bytes = frame_bytes;
-  }
+  HIP_TRY(m->frame.reserve(frame_bytes, {hs}), "hipMalloc frame");
+  double* d_frame = m->frame.get<double>();
   std::vector<Progress> pr((size_t)(progress ? n : 0));
-  struct FreeAll { std::vector<Progress>& v; ~FreeAll() { for (auto& x : v) free_progress(x); } } free_all{pr};
   uint64_t total_px = 0;
   std::vector<Progress*> pp;
   for (int d = 0; d < (int)pr.size(); ++d) {
@@ -563,20 +488,19 @@ int yart_render_multi(yart_multi* m, const yart_camera* cam, const yart_render_p
     pp.push_back(&pr[(size_t)d]);
   }
   // everything (renders, gather, unpack) is enqueued before the host waits
-  if (int rc = multi_submit(m, cam, p, m->frame, hs, progress ? &pr : nullptr)) return rc;
+  if (int rc = multi_submit(m, cam, p, d_frame, hs, progress ? &pr : nullptr)) return rc;
   HIP_TRY(hipSetDevice(m->devices[0]), "hipSetDevice");
-  hipEvent_t done;
-  HIP_TRY(hipEventCreateWithFlags(&done, hipEventDisableTiming), "hipEventCreate");
-  std::unique_ptr<std::remove_pointer<hipEvent_t>::type, decltype(&hipEventDestroy)> hold(done, &hipEventDestroy);
+  Event done;
+  HIP_TRY(done.create(), "hipEventCreate");
   HIP_TRY(hipEventRecord(done, hs), "hipEventRecord");
   if (int rc = wait_with_progress({done}, {m->devices[0]}, pp, total_px, progress, user)) return rc;
   HIP_TRY(hipSetDevice(m->devices[0]), "hipSetDevice");
-  HIP_TRY(hipMemcpyAsync(xyz_sum_out, m->frame, frame_bytes, hipMemcpyDeviceToHost, hs), "copy frame");
+  HIP_TRY(hipMemcpyAsync(xyz_sum_out, d_frame, frame_bytes, hipMemcpyDeviceToHost, hs), "copy frame");
   HIP_TRY(hipStreamSynchronize(hs), "copy frame");
   uint32_t frames = 0;
   // the host stream's slot is idle now: the timing of its frame
   double r = 0.0, g = 0.0;
-  if (int rc = multi_timing(m, m->slots[hs].get(), &r, &g, &frames)) return rc;
+  if (int rc = multi_timing(m, m->latest, &r, &g, &frames)) return rc;
   m->render_ms = frames ? r / frames : 0.0;
   m->gather_ms = frames ? g / frames : 0.0;
   return ok();
@@ -614,7 +538,7 @@ int yart_multi_query(yart_multi* m, int32_t* state, int32_t* unpacked) {
   auto done = [](hipEvent_t e) { return e && hipEventQuery(e) == hipSuccess; };
   for (int d = 0; d < m->n; ++d) {
     (void)hipSetDevice(m->devices[(size_t)d]);
-    state[d] = done(S.gathered[(size_t)d]) ? 2 : done(S.rendered[(size_t)d]) ? 1 : 0;
+    state[d] = done(S.dev[(size_t)d].gathered) ? 2 : done(S.dev[(size_t)d].rendered) ? 1 : 0;
   }
   (void)hipSetDevice(m->devices[0]);
   *unpacked = done(S.done) ? 1 : 0;

@@ -10,6 +10,7 @@
 #include <vector>
 
 #include "../../include/yart.h"
+#include "hip_raii.h"
 #include "kernels.h"
 
 namespace yart_impl {
@@ -37,35 +38,30 @@ class DeviceGuard {  // keep the caller's current device (torch tracks its own)
 // their passes over the shared scratch; the stream then orders the frames on the device.
 struct StreamState {
   std::mutex frame_mu;
-  double* scratch = nullptr;  // per-sample XYZ of the chunked path + the unit counter at its end
-  size_t bytes = 0;
+  DevBuf scratch;  // per-sample XYZ of the chunked path + the unit counter at its end
   // wavefront path (mesh scenes): two path queues of `wf_pool` slots, the queue counters and the
   // host-mapped status ring the iterations report into
-  void* wf_mem = nullptr;
-  size_t wf_bytes = 0;
+  DevBuf wf_mem;
   uint32_t wf_pool = 0;
-  uint32_t* wf_status_host = nullptr;
-  uint32_t* wf_status_dev = nullptr;
+  HostMapped wf_status;
   uint64_t wf_iter = 0;  // wavefront iterations launched on this stream so far (status-ring slot numbering)
   // deep meshes on the megakernel: the walk stacks' HBM overflow, kOvfWords per wave of a launch
-  uint32_t* ovf = nullptr;
-  size_t ovf_bytes = 0;
+  DevBuf ovf;
   // frames of more than one scratch pass (capi.cpp launch_frame): the odd passes render on `aux`
   // into the scratch's second half while the even ones finish on the caller's stream, and `acc`
   // adds the passes in order; created with the stream's first such frame
-  hipStream_t aux = nullptr, acc = nullptr;
-  hipEvent_t ev_start = nullptr, ev_render[2] = {nullptr, nullptr}, ev_acc[2] = {nullptr, nullptr};
+  Stream aux, acc;
+  Event ev_start, ev_render[2], ev_acc[2];
 };
 
 // Progress of one frame (yart_render's callback): the kernels store `base + units handed out` to
 // a host-mapped word; the calling thread polls it while the stream runs (main.rs:720-721 sends a
 // Progress message per rendered row instead).
 struct Progress {
-  uint32_t* host = nullptr;    // host view (hipHostMalloc, coherent)
-  uint32_t* device = nullptr;  // the kernels' view of the same word
-  uint32_t* counter = nullptr; // device memory: finished units of the fused path (atomic)
-  uint32_t total_units = 0;    // over all passes of the frame
-  uint64_t pixels = 0;         // covered pixels of the shard
+  HostMapped word;           // the host's and the kernels' view of the same word
+  DevBuf counter;            // device memory: finished units of the fused path (atomic)
+  uint32_t total_units = 0;  // over all passes of the frame
+  uint64_t pixels = 0;       // covered pixels of the shard
 };
 
 }  // namespace yart_impl
@@ -77,15 +73,15 @@ struct yart_scene {
   bool wavefront = false;  // mesh scene without EXT features: k_wf_shade / k_wf_trace (deep meshes, YART_OPT_MESH_WAVEFRONT)
   uint32_t wf_pool = 1u << 20;  // paths in flight (YART_OPT_WF_POOL)
   yart_dev::DevScene dev{};
-  std::vector<void*> owned;
+  std::vector<yart_impl::DevBuf> owned;  // the uploaded scene
   yart_scene_info info{};
   std::mutex mu;  // guards the maps and pools below (never held across a device wait)
   std::map<hipStream_t, std::unique_ptr<yart_impl::StreamState>> streams;
   std::vector<hipStream_t> idle_streams;   // library-owned streams for the host-output calls
-  std::vector<hipStream_t> owned_streams;
+  std::vector<yart_impl::Stream> owned_streams;
   // kernel-boundary events of the frames launched per stream and not yet read (yart_frame_timing)
-  std::map<hipStream_t, std::vector<std::vector<hipEvent_t>>> frames;
-  std::vector<hipEvent_t> event_pool;
+  yart_impl::EventPool event_pool;
+  std::map<hipStream_t, std::vector<yart_impl::EventPool::Lease>> frames;
   ~yart_scene();
 };
 
@@ -96,15 +92,25 @@ int make_args(const yart_scene* s, const yart_camera* cam, const yart_render_par
 // Enqueue one frame (all passes) on `stream`. prog: optional progress word (fills total_units).
 int launch_frame(yart_scene* s, yart_dev::RenderArgs a, uint32_t requested, bool stats, hipStream_t stream,
                  Progress* prog);
-// A library-owned non-blocking stream of the scene's device, exclusively the caller's until returned.
-int acquire_stream(yart_scene* s, hipStream_t* out);
-void release_stream(yart_scene* s, hipStream_t st);
+// A library-owned non-blocking stream of the scene's device, exclusively the holder's: synchronized
+// and returned to the scene's idle streams when the lease goes.
+class StreamLease {
+ public:
+  explicit StreamLease(yart_scene* s) : s_(s) {}
+  StreamLease(const StreamLease&) = delete;
+  StreamLease& operator=(const StreamLease&) = delete;
+  ~StreamLease();
+  int acquire();
+  operator hipStream_t() const { return st_; }
+ private:
+  yart_scene* s_;
+  hipStream_t st_ = nullptr;
+};
 // Covered pixels (main.rs:636-647 crop grid) of the blocks a shard owns.
 uint64_t shard_pixels(uint32_t w, uint32_t h, uint32_t shard_index, uint32_t shard_count);
 // Wait for `done` on the calling thread, reporting progress from the given words (one per device).
 int wait_with_progress(const std::vector<hipEvent_t>& done, const std::vector<int>& devices,
                        const std::vector<Progress*>& prog, uint64_t total_pixels, yart_progress_fn fn, void* user);
-int alloc_progress(Progress& p);
-void free_progress(Progress& p);
+int alloc_progress(Progress& p);  // on the current device
 
 }  // namespace yart_impl
